@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- BPR triplets/s of the fused MI355X BPR-MF training step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ml10m|ml1m|ml100k|lfm2b|hbm]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ml10m|ml1m|ml100k|lfm2b|hbm] [--full]
+                    [--dump-outputs DIR]
 
 One "step" = one full training step of Trainer.fit on one batch of synthetic interactions: on-device
 uniform rejection sampling of the negatives, embedding gathers, (u.i - u.j) scores with item bias,
@@ -10,17 +11,23 @@ torch.optim.AdamW).  Inputs (tables, interaction CSR/COO, the epoch permutation)
 before the timed region.  Default workload: BASELINE.json configs[2] (ml10m shape, D=512, N=100,
 B=4096) -- the configuration the metric "% HBM-read roofline at dim=512" is quoted on.
 
-Rank 0 prints ONE JSON line (see the driver contract).  Besides the contract's keys it carries, all timed inside
-this run:
+Rank 0 prints ONE JSON line (see the driver contract).  A plain run sets up, warms up, times the K steps and prints the
+line: the contract's keys, plus
   roofline      the gather+BPR kernel (k_fwd_ugrad) of the headline workload: algorithmic read bytes per launch / its
                 mean duration (HIP events of the kernel's own dispatch on the launch stream, inside the timed region).
-                At the ml10m shape the tables live in L2 + Infinity Cache, so the bound is the cache fabric, not HBM
+                At the ml10m shape the tables live in L2 + Infinity Cache, so the bound is the cache fabric, not HBM.
+                (Workloads run as replayed graphs, B < 2048, have no events in the timed region: their roofline needs
+                the extra eager pass of --full and is null in a plain run.)
+--dump-outputs DIR writes what the timed path computed by its last step (the trained tables and the last loss) as
+DIR/<name>.npy; see dump_outputs.  With --full the line also carries, all timed inside this run:
+  pure_gather   (inside roofline) the forward with the lazy rows' catch-up in a launch of its own, 32 further steps
   workloads     (N=1) the other BASELINE training configs -- ml1m (configs[1]), ml100k (configs[0]) -- and `hbm`,
                 the same step on tables no cache can hold, whose roofline IS the HBM-read roofline of the kernel
   eval          full-catalogue evaluation users/s (ml10m and lfm2b shapes at N=1; item-sharded lfm2b at N>1)
   cpu_baseline  (N=1) the CPU restatement of the reference's trainer (oracle/cpu_trainer.py, kind "port"): a bounded
                 sample of the headline workload + the SURVEY 8(d) protocol on configs[0] (20 + 200 steps, 0 and 4
                 loader workers)
+  and (N=1) workloads.cfg5_shard, sharded_1rank, ieee_build, as_given_protocol: see main().
 N > 1 (one process per GPU, RCCL): item table range-sharded, user table row-sharded, global batch N*B (weak scaling).
 """
 import os
@@ -92,6 +99,27 @@ def pmc_fetch_bytes(kernel_prefix, workload, key=None):
         if name.startswith(kernel_prefix) and 'FETCH_SIZE_KB_mean' in row:
             return row.get(key) if key else 2.0 * row['FETCH_SIZE_KB_mean'] * 1024.0
     return None
+
+
+DUMP_ROW_BYTES = {1: 4 << 20, 2: 28 << 20}   # --dump-outputs: bytes per written array, by rank (60 MiB in all at most)
+
+
+def dump_outputs(out_dir, tables, loss):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the trained tables (float32) and
+    that step's loss (float64 [1]) -- as out_dir/<name>.npy.  A table larger than DUMP_ROW_BYTES is written as a
+    sample of its rows: the same rows in every run (numpy RandomState(0), ascending), so two builds of the project
+    compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in tables.items():
+        if t is None:
+            continue
+        row_bytes = 4 * (t[0].numel() if t.dim() > 1 else 1)
+        k = DUMP_ROW_BYTES[min(t.dim(), 2)] // row_bytes
+        if t.shape[0] > k:
+            rows = np.sort(np.random.RandomState(0).choice(t.shape[0], k, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(out_dir, name + '.npy'), t.detach().to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, 'loss.npy'), np.array([loss], dtype=np.float64))
 
 
 def init_tables(U, I, D, device, seed=64):
@@ -181,10 +209,11 @@ def native_step_self_check(data, D, B, N, device, comm, order, n_steps=3):
 # one training workload
 # ------------------------------------------------------------------------------------------------
 def run_training(workload, device, steps, warmup, comm=None, prefetch=True, lazy_users='auto', all_stages=False,
-                 pure_gather=True, strict=False):
+                 pure_gather=True, strict=False, extras=True, dump_dir=None):
     """-> dict(value, ms_per_step, fwd_us, fwd_launches, loss, B, N, D, data, csr, timing).  Timed exactly as the
     contract says: W warm-up steps, barrier + synchronize, K steps (+ the flush of lazily updated rows), barrier +
-    synchronize; MAX over ranks."""
+    synchronize; MAX over ranks.  extras=False: nothing runs after the timed region (no pure-gather pass, no eager pass
+    that event-times the forward of a replayed workload).  dump_dir: dump_outputs() of the state the timed region left."""
     from hassaku_amd.data import synthetic
     shape, D, N, B = WORKLOADS[workload]
     world = 1 if comm is None else comm.world
@@ -276,19 +305,30 @@ def run_training(workload, device, steps, warmup, comm=None, prefetch=True, lazy
     elapsed = time.perf_counter() - t0
     flush_us = ev_f0.elapsed_time(ev_f1) * 1e3
     st.disable_timing()
+    if dump_dir is not None:
+        st.check_status('timed region')
+        loss = st.last_loss()
+        if comm is None:
+            tables = st.params
+        else:                                                     # collectives: every rank assembles, rank 0 writes
+            (user_emb, _), (item_emb, item_bias) = st.gather_user_table(), st.gather_item_table()
+            tables = dict(user_emb=user_emb, item_emb=item_emb, item_bias=item_bias)
+        if comm is None or comm.rank == 0:
+            dump_outputs(dump_dir, tables, loss)
+        del tables
     if comm is not None:                                          # the slowest rank defines the step time
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         comm.all_reduce(t, op='max')
         elapsed = float(t.item())
     n_replays = st.graph_replays() if comm is None else 0
-    if replayed:
+    if replayed and extras:
         st.enable_timing(('fwd',), every=1)
         run(64, warmup + steps)
         fence()
         st.disable_timing()
     timing = st.collect_timing()
     pure_us = None
-    if comm is None and not replayed and st.st.lazy_users and pure_gather:
+    if comm is None and not replayed and st.st.lazy_users and pure_gather and extras:
         # the forward as a pure gather: the pending zero-gradient AdamW steps of the batch's user rows replayed by a
         # stand-alone launch instead of inside the forward's registers (slower step, same results)
         st.st.catchup_apart = 1
@@ -837,18 +877,24 @@ def main():
     ap.add_argument('--workload', default='ml10m', choices=sorted(WORKLOADS) + ['cfg5'],
                     help="cfg5 = BASELINE configs[4] (100 M x 10 M, D=1024): the job itself with --gpus 8, one rank's "
                          "share of it (rank 3 of 8, collectives stubbed) with --gpus 1")
-    ap.add_argument('--cpu-budget', type=float, default=12.0, help='seconds of CPU-baseline work on the headline workload (0 = skip every CPU leg)')
+    ap.add_argument('--full', action='store_true', help='everything besides the headline: CPU baseline, pure-gather pass, the '
+                    'forward event-timed after a replayed timed region, and (without --only) the other workloads, evaluation '
+                    'legs, child-process legs and the as-given protocol.  Off: set up, warm up, time --steps, print the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what they computed (tables, last loss) as DIR/<name>.npy')
+    ap.add_argument('--cpu-budget', type=float, default=12.0, help='with --full: seconds of CPU-baseline work on the headline workload (0 = skip every CPU leg)')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for --gpus > 1 ('nccl' = RCCL; 'gloo' "
                     "stages collectives through the host and lets several ranks share one GPU: functional rehearsal only)")
     ap.add_argument('--no-prefetch', action='store_true', help='do not prepare (sample + sort) the next batch on a side stream during the current step')
     ap.add_argument('--dense-users', action='store_true', help='dense AdamW sweep over the user table every step')
     ap.add_argument('--lazy-users', action='store_true', help='lazy, exact user AdamW whatever the table size')
     ap.add_argument('--time-all-stages', action='store_true', help='event-time every stage (perturbs the step time)')
-    ap.add_argument('--only', action='store_true', help='headline workload only: no extra workloads, no eval legs')
+    ap.add_argument('--only', action='store_true', help='with --full: headline workload only: no extra workloads, no eval legs')
     ap.add_argument('--no-pure-gather', action='store_true', help='skip the extra pure-gather timing pass (profiling: keeps the kernel averages of the timed region unmixed)')
     ap.add_argument('--eval-only', default=None, choices=sorted(EVAL_SHAPES), help='only the evaluation leg of this shape (profiling)')
     ap.add_argument('--sharded', action='store_true', help='N=1 through the multi-GPU code path (1-rank process group)')
-    ap.add_argument('--with-eval', action='store_true', help='with --only: the item-sharded lfm2b evaluation leg as well')
+    ap.add_argument('--with-eval', action='store_true', help='without the other legs (plain run, or --full --only): the '
+                    'item-sharded lfm2b evaluation leg as well')
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -857,8 +903,10 @@ def main():
     if world != args.gpus:
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run')
 
+    if args.dump_outputs and (args.workload == 'cfg5' or args.eval_only):
+        raise SystemExit('--dump-outputs writes the outputs of the training workloads only (not cfg5 / --eval-only)')
     cpu = None
-    if world == 1 and args.cpu_budget > 0:
+    if args.full and world == 1 and args.cpu_budget > 0:
         cpu = cpu_baseline(args.workload, args.cpu_budget)        # before anything initialises the GPU
 
     if not torch.cuda.is_available():
@@ -905,10 +953,11 @@ def main():
     # 169 GB share of configs[4] gathers random 4 KB rows out of tables that large, and it ran 9 % slower (item pass 5.57
     # against 4.92 ms) as a child of a parent that had already been through its other legs than from a fresh process.
     children = {}
-    if comm is not None and world == CFG5['world'] and not args.only and args.workload != 'cfg5':
+    extra_legs = args.full and not args.only
+    if comm is not None and world == CFG5['world'] and extra_legs and args.workload != 'cfg5':
         # (the same for the one place the whole configs[4] job can run: before this process's other legs)
         children['cfg5'] = guarded(run_cfg5, device, 12, 4, comm)
-    if comm is None and not args.only:
+    if comm is None and extra_legs:
         # BASELINE configs[4] needs 8 GPUs; what one GPU can show is one rank's full-size share of it
         children['cfg5_shard'] = guarded(run_cfg5_share_child, device)
         # the multi-GPU code path on this one GPU (a 1-rank RCCL group: every kernel, every collective call and stream
@@ -917,7 +966,8 @@ def main():
         children['ieee_build'] = guarded(run_ieee_build_child, device, args.steps, args.warmup)
     r = run_training(args.workload, device, args.steps, args.warmup, comm=comm, prefetch=not args.no_prefetch,
                      lazy_users=False if args.dense_users else True if args.lazy_users else 'auto',
-                     all_stages=args.time_all_stages, pure_gather=not args.no_pure_gather)
+                     all_stages=args.time_all_stages, pure_gather=not args.no_pure_gather, extras=args.full,
+                     dump_dir=args.dump_outputs)
     out = {
         'metric': 'BPR triplets/sec', 'value': r['value'], 'unit': 'triplets/s', 'n_gpus': world, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': r['ms_per_step'], 'higher_is_better': True, 'scaling': 'weak',
@@ -949,9 +999,9 @@ def main():
     if 'stage_us_per_step' in r:
         out['stage_us_per_step'] = r['stage_us_per_step']
 
-    if args.only and args.with_eval and comm is not None:
+    if args.with_eval and not extra_legs and comm is not None:
         out['eval'] = {'lfm2b': run_eval('lfm2b', device, comm)}
-    if not args.only:
+    if extra_legs:
         if comm is None:
             # the other BASELINE training configs + the HBM-resident point, each on the same clock as the headline
             out['workloads'] = {}

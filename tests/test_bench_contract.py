@@ -1,4 +1,5 @@
-"""The driver's contract with bench.py: one JSON line, the agreed keys, the roofline and cpu_baseline objects."""
+"""The driver's contract with bench.py: one JSON line, the agreed keys, the roofline and cpu_baseline objects (--full),
+the outputs of the timed path (--dump-outputs)."""
 import json
 import os
 import subprocess
@@ -13,8 +14,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--workload', 'ml100k', '--steps', '6',
-                          '--warmup', '2', '--cpu-budget', '1', '--only'], cwd=REPO, capture_output=True, text=True,
-                         timeout=600)
+                          '--warmup', '2', '--cpu-budget', '1', '--only', '--full'], cwd=REPO, capture_output=True,
+                         text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1
@@ -41,6 +42,33 @@ def test_bench_prints_one_contract_line():
     # configs[0], 20 warm-up + 200 timed steps, with 0 and with 4 loader workers
     assert [leg['train_n_workers'] for leg in c['legs']] == [0, 4]
     assert all(leg['steps'] >= 200 and leg['warmup'] == 20 and leg['value'] > 0 for leg in c['legs'])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full: the contract's keys and nothing that takes work of its own (no CPU baseline, no other legs);
+    --dump-outputs writes the timed path's tables and last loss as float32 / float64 .npy files."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--workload', 'ml100k',
+                          '--steps', '6', '--warmup', '2', '--dump-outputs', str(tmp_path)], cwd=REPO,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup'):
+        assert k in d, k
+    assert d['steps'] == 6 and d['warmup'] == 2
+    assert abs(d['value'] * d['ms_per_step'] * 1e-3 - 128 * 1) < 1e-6 * 128      # B=128, N=1
+    for k in ('cpu_baseline', 'workloads', 'eval', 'sharded_1rank', 'ieee_build', 'as_given_protocol'):
+        assert k not in d, k
+    files = sorted(os.listdir(tmp_path))
+    assert files == ['item_bias.npy', 'item_emb.npy', 'loss.npy', 'user_emb.npy'], files
+    arrays = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert arrays['user_emb'].shape == (943, 64) and arrays['item_emb'].shape == (1682, 64)   # whole tables at this size
+    assert arrays['item_bias'].shape == (1682,) and arrays['loss'].shape == (1,)
+    assert float(arrays['loss'][0]) == d['config']['loss_last_step']
 
 
 @pytest.mark.gpu

@@ -23,13 +23,13 @@ case $MODE in
   env)
     ARGS=$1; shift
     for i in 1 2 3; do for e in "$@"; do
-      env $e python bench.py --cpu-budget 0 --only --no-pure-gather $ARGS 2>/dev/null |
+      env $e python bench.py --full --cpu-budget 0 --only --no-pure-gather $ARGS 2>/dev/null |
         line "$e" "round(d['ms_per_step']*1e3,2), 'us/step, fwd', round(d['roofline']['avg_us'],2)" || exit 1
     done; done ;;
   lib)
     ARGS=$1; OTHER=$2
     for i in 1 2 3; do for lib in $OTHER libhassaku_hip.so; do
-      HSK_LIB_PATH=$PWD/hassaku_amd/$lib python bench.py --cpu-budget 0 --only --no-pure-gather $ARGS 2>/dev/null |
+      HSK_LIB_PATH=$PWD/hassaku_amd/$lib python bench.py --full --cpu-budget 0 --only --no-pure-gather $ARGS 2>/dev/null |
         line "$lib" "round(d['ms_per_step']*1e3,2), 'us/step, fwd', round(d['roofline']['avg_us'],2)" || exit 1
     done; done ;;
   eval)
@@ -41,7 +41,7 @@ case $MODE in
   stages)
     ARGS=$1; shift
     for e in "$@"; do
-      env $e python bench.py --cpu-budget 0 --only --no-pure-gather --time-all-stages $ARGS 2>/dev/null |
+      env $e python bench.py --full --cpu-budget 0 --only --no-pure-gather --time-all-stages $ARGS 2>/dev/null |
         line "$e" "round(d['ms_per_step']*1e3,1), 'us/step', {k: round(v,1) for k,v in d['stage_us_per_step'].items()}" || exit 1
     done ;;
   *) echo "usage: see the head of tools/ab.sh"; exit 2 ;;

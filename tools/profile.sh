@@ -12,7 +12,7 @@ rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 case "$*" in
   *--eval-only*) ARGS="$@" ;;
-  *) ARGS="--cpu-budget 0 --only --no-pure-gather $@" ;;   # e.g. "--steps 20 --warmup 5", "--workload hbm --steps 24 --warmup 8"
+  *) ARGS="--full --cpu-budget 0 --only --no-pure-gather $@" ;;   # e.g. "--steps 20 --warmup 5", "--workload hbm --steps 24 --warmup 8"
 esac
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS > $OUT/bench_trace.log 2>&1 || exit 1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $ROOT/bench.py $ARGS > $OUT/bench_fetch.log 2>&1 || exit 1

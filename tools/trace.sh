@@ -14,7 +14,7 @@ i=0
 for e in "$@"; do
   i=$((i+1))
   OUT=$ROOT/gpurun_out/prof_trace$i; rm -rf $OUT; mkdir -p $OUT
-  env $e rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --cpu-budget 0 $ARGS > $OUT/bench_trace.log 2>&1 || { tail -5 $OUT/bench_trace.log; exit 1; }
+  env $e rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --cpu-budget 0 $ARGS > $OUT/bench_trace.log 2>&1 || { tail -5 $OUT/bench_trace.log; exit 1; }
   echo "== $e: $(grep -o '"ms_per_step": [0-9.]*' $OUT/bench_trace.log | head -1)"
   python3 $ROOT/tools/timeline.py $OUT/trace $ANCHOR 2 || true
   python3 $ROOT/tools/kstats.py $OUT/trace 10 || true
