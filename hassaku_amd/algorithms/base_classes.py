@@ -1,7 +1,9 @@
-"""Plugin base classes with the reference's method names (algorithms/base_classes.py:12-52,88-165).
+"""Plugin base classes with the reference's method names (algorithms/base_classes.py:12-165).
 
-Only the SGD family is in scope; the sparse-matrix family keeps its abstract
-interface so that out-of-scope algorithms written against it still type-check.
+Two families: `SGDBasedRecommenderAlgorithm` (trained by `Trainer`) and `SparseMatrixBasedRecommenderAlgorithm`
+(fitted once on the binary train matrix: ItemKNN / UserKNN, algorithms/knn_algs.py).  Where the reference keeps a
+dense float64 `pred_mtx` on the host, a sparse-matrix model here scores chunks of user rows on the device
+(`score_rows`); `predict` gathers from those rows and returns float64 like the reference's.
 """
 import abc
 import logging
@@ -35,6 +37,30 @@ class RecommenderAlgorithm(abc.ABC):
     @abc.abstractmethod
     def build_from_conf(conf: dict, dataset):
         ...
+
+
+class SparseMatrixBasedRecommenderAlgorithm(RecommenderAlgorithm):
+    """Models fitted on the user x item sparse matrix (algorithms/base_classes.py:55-85).  Subclasses implement
+    `fit(matrix)` (a scipy CSR or a `UserItemCsr`) and `score_rows(u_idxs, excl=None)` -> float64 [B, n_items] on the
+    device; `excl` = (indptr, indices) of an exclusion CSR whose columns come back as -inf."""
+
+    def __init__(self):
+        super().__init__()
+        self.name = 'SparseMatrixBasedRecommenderAlgorithm'
+
+    @abc.abstractmethod
+    def fit(self, matrix):
+        ...
+
+    @abc.abstractmethod
+    def score_rows(self, u_idxs: torch.Tensor, excl=None) -> torch.Tensor:
+        ...
+
+    @torch.no_grad()
+    def predict(self, u_idxs: torch.Tensor, i_idxs: torch.Tensor) -> torch.Tensor:
+        """float64 scores [B, n] of users u_idxs [B] on items i_idxs [B, n] (pred_mtx[u_idxs[:, None], i_idxs])."""
+        rows = self.score_rows(u_idxs)
+        return torch.gather(rows, 1, i_idxs.to(rows.device, torch.int64))
 
 
 class SGDBasedRecommenderAlgorithm(RecommenderAlgorithm, nn.Module):

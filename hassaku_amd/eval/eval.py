@@ -4,7 +4,9 @@
 HIP matrix-factorisation model it does not densify anything on the host: per chunk of users it runs
 hsk_mf_eval_topk (fp32-MFMA scores of the chunk against the item table, -inf on the user's excluded items
 read from the exclude CSR, top-100) and hsk_rank_metrics (precision / recall / ndcg at 5,10,50,100 from
-the ground-truth CSR), then accumulates per-group sums exactly as FullEvaluator does.  Any other
+the ground-truth CSR), then accumulates per-group sums exactly as FullEvaluator does.  A sparse-matrix model
+(ItemKNN / UserKNN) scores chunks of users into float64 rows on the device (hsk_knn_score_rows, excluded items -inf),
+then hsk_knn_topk_rows and hsk_rank_metrics (eval/eval.py:222-236 there: float64 scores, topk(100)).  Any other
 `RecommenderAlgorithm` goes through the generic dense path (predict -> mask -> eval_batch).
 """
 from collections import defaultdict
@@ -14,7 +16,8 @@ import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import RecommenderAlgorithm, SGDBasedRecommenderAlgorithm
+from hassaku_amd.algorithms.base_classes import (RecommenderAlgorithm, SGDBasedRecommenderAlgorithm,
+                                                  SparseMatrixBasedRecommenderAlgorithm)
 from hassaku_amd.eval.metrics import ndcg_at_k_batch, precision_at_k_batch, recall_at_k_batch
 from hassaku_amd.utilities.utils import log_info_results
 
@@ -113,6 +116,26 @@ def _hip_mf_eval(alg, dataset, evaluator: FullEvaluator, device, chunk: int):
     alg.check_indices()
 
 
+SPARSE_EVAL_CHUNK_BYTES = 1 << 29   # float64 score rows of one chunk of users
+
+
+def _hip_sparse_eval(alg, dataset, evaluator: FullEvaluator, device):
+    arrays = dataset.device_arrays(device)
+    ks = sorted(evaluator.K_VALUES, reverse=True)
+    k_max = ks[0]
+    if dataset.n_items < k_max:
+        raise ValueError(f'full evaluation needs at least {k_max} items (K_VALUES), got {dataset.n_items}')
+    chunk = max(1, min(dataset.n_users, SPARSE_EVAL_CHUNK_BYTES // (8 * dataset.n_items)))
+    buf = torch.empty((chunk, dataset.n_items), dtype=torch.float64, device=device)
+    for lo in range(0, dataset.n_users, chunk):
+        u = torch.arange(lo, min(lo + chunk, dataset.n_users), device=device)
+        scores = alg.score_rows(u, excl=(arrays['excl_indptr'], arrays['excl_indices']), out=buf[:len(u)])
+        _, ids = hip_ops.knn_topk_rows(scores, k_max)
+        met = hip_ops.rank_metrics(ids, u, arrays['label_indptr'], arrays['label_indices'], ks)
+        evaluator.eval_ranked(u, met, ks)
+    alg.check_indices()
+
+
 def evaluate_recommender_algorithm(alg: RecommenderAlgorithm, eval_loader, evaluator: FullEvaluator, device='cpu',
                                    verbose=False):
     from hassaku_amd.algorithms.sgd_alg import SGDMatrixFactorization
@@ -127,6 +150,9 @@ def evaluate_recommender_algorithm(alg: RecommenderAlgorithm, eval_loader, evalu
             # hip_ops.FUSED_TOPK_MIN_ITEMS columns) materialise chunk x n_items scores: at most 2 GB per chunk
             chunk = max(int(getattr(eval_loader, 'batch_size', 256) or 256), 16384)
             _hip_mf_eval(alg, dataset, evaluator, dev, chunk)
+    elif isinstance(alg, SparseMatrixBasedRecommenderAlgorithm):
+        with torch.no_grad():
+            _hip_sparse_eval(alg, dataset, evaluator, alg.device)
     elif isinstance(alg, SGDBasedRecommenderAlgorithm) and hasattr(alg, 'lookup'):
         # the other SGD models: item representations once, then every user batch against them (eval/eval.py:237-248);
         # top-k and metrics on the device as for any dense score matrix

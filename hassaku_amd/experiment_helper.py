@@ -1,15 +1,17 @@
-"""Train / validate / test orchestration -- the reference's experiment_helper.py:18-130 for the SGD family.
+"""Train / validate / test orchestration -- the reference's experiment_helper.py:18-130.
 
-Same three entry points and the same conf contract; wandb is optional (used only if importable and
+Same three entry points and the same conf contract (the sparse-matrix branch, experiment_helper.py:48-65 there, fits
+ItemKNN / UserKNN on the train CSR and evaluates on the device); wandb is optional (used only if importable and
 `running_settings.use_wandb` is true).  Unlike the reference's run_test (which evaluates on the CPU because
 it passes no device, experiment_helper.py:116-117), the test split is scored on the HIP device.
 """
 import typing
 
 from hassaku_amd.algorithms.algorithms_utils import AlgorithmsEnum
-from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm
+from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm, SparseMatrixBasedRecommenderAlgorithm
 from hassaku_amd.conf.conf_parser import parse_conf, parse_conf_file, save_yaml
 from hassaku_amd.data.data_utils import DatasetsEnum, get_dataloader
+from hassaku_amd.data.dataset import TrainRecDataset
 from hassaku_amd.eval.eval import FullEvaluator, evaluate_recommender_algorithm
 from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 from hassaku_amd.train.trainer import Trainer
@@ -67,6 +69,23 @@ def run_train_val(alg: AlgorithmsEnum, dataset: DatasetsEnum, conf: typing.Union
     if wandb is not None:
         wandb.init(config=conf, tags=[alg.name, dataset.name], name=conf['time_run'], job_type='train/val')
     reproducible(conf['running_settings']['seed'])
+    if issubclass(alg.value, SparseMatrixBasedRecommenderAlgorithm):
+        if world > 1:
+            raise ValueError(f'{alg.name} runs in a single process')
+        train_dataset = TrainRecDataset(conf['dataset_path'])
+        val_loader = get_dataloader(conf, 'val')
+        model = alg.value.build_from_conf(conf, train_dataset)
+        model.fit(train_dataset.sampling_csr)
+        evaluator = FullEvaluator(aggr_by_group=True, n_groups=val_loader.dataset.n_user_groups,
+                                  user_to_user_group=val_loader.dataset.user_to_user_group)
+        metrics_values = evaluate_recommender_algorithm(model, val_loader, evaluator, model.device,
+                                                        verbose=conf['running_settings']['batch_verbose'])
+        model.save_model_to_path(conf['model_path'])
+        save_yaml(conf['model_path'], conf)
+        if wandb is not None:
+            wandb.log(metrics_values)
+            wandb.finish()
+        return metrics_values, conf
     if not issubclass(alg.value, SGDBasedRecommenderAlgorithm):
         raise ValueError(f'Training for {alg.value} has been not implemented')
     train_loader = get_dataloader(conf, 'train')
@@ -90,11 +109,16 @@ def run_test(alg: AlgorithmsEnum, dataset: DatasetsEnum, conf: typing.Union[str,
     if wandb is not None:
         wandb.init(config=conf, tags=[alg.name, dataset.name], name=conf['time_run'], job_type='test', reinit=True)
     test_loader = get_dataloader(conf, 'test')
-    model = alg.value.build_from_conf(conf, test_loader.dataset).to(conf.get('device', 'cuda'))
+    model = alg.value.build_from_conf(conf, test_loader.dataset)
+    if isinstance(model, SparseMatrixBasedRecommenderAlgorithm):
+        device = model.device
+    else:
+        device = conf.get('device', 'cuda')
+        model = model.to(device)
     model.load_model_from_path(conf['model_path'])
     evaluator = FullEvaluator(aggr_by_group=True, n_groups=test_loader.dataset.n_user_groups,
                               user_to_user_group=test_loader.dataset.user_to_user_group)
-    metrics_values = evaluate_recommender_algorithm(model, test_loader, evaluator, conf.get('device', 'cuda'),
+    metrics_values = evaluate_recommender_algorithm(model, test_loader, evaluator, device,
                                                     verbose=conf['running_settings']['batch_verbose'])
     if wandb is not None:
         wandb.log(metrics_values, step=0)

@@ -744,3 +744,116 @@ def rank_metrics(topk_idx: torch.Tensor, u_idx: torch.Tensor, label_indptr: torc
                                     _p(label_indices), ks_arr,
                                     len(ks), _p(out), _stream()), 'hsk_rank_metrics')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# ItemKNN / UserKNN (hsk_knn.hip)
+# ---------------------------------------------------------------------------------------------------
+KNN_KINDS = {'cosine': 0, 'jaccard': 1, 'sorensen_dice': 2, 'asymmetric_cosine': 3, 'tversky': 4}
+KNN_MAX_K = 1024
+KNN_MAX_WINDOW = 20480
+
+
+def knn_pack_dims(n_rows: int, n_cols: int) -> Tuple[int, int]:
+    """(rows_pad, k_pad) of the int8 entity operand of an [n_rows, n_cols] binary matrix."""
+    lib = _lib.load()
+    rp, kp = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(lib.hsk_knn_pack_dims(int(n_rows), int(n_cols), ctypes.byref(rp), ctypes.byref(kp)), 'hsk_knn_pack_dims')
+    return rp.value, kp.value
+
+
+def knn_pack_i8(indptr: torch.Tensor, indices: torch.Tensor, n_rows: int, n_cols: int) -> torch.Tensor:
+    """Binary CSR -> dense int8 [rows_pad, k_pad] (zero padded)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(indptr, torch.int64, 'indptr', (n_rows + 1,))
+    _chk(indices, torch.int32, 'indices')
+    rp, kp = knn_pack_dims(n_rows, n_cols)
+    out = torch.empty((rp, kp), dtype=torch.int8, device=indptr.device)
+    _lib.check(lib.hsk_knn_pack_i8(_p(indptr), _p(indices), n_rows, n_cols, rp, kp, _p(out), _stream()),
+               'hsk_knn_pack_i8')
+    return out
+
+
+def knn_gram_i8(M: torch.Tensor, n_rows: int, r0: int, r1: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 counts C[r - r0, c] = <M[r], M[c]> for r in [r0, r1), c < n_rows (r0 a multiple of 128)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(M, torch.int8, 'M')
+    rp, kp = M.shape
+    if out is None:
+        out = torch.empty((r1 - r0, n_rows), dtype=torch.int32, device=M.device)
+    _chk(out, torch.int32, 'out')
+    if out.dim() != 2 or out.shape[0] < r1 - r0 or out.shape[1] < n_rows:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({r1 - r0}, {n_rows})')
+    _lib.check(lib.hsk_knn_gram_i8(_p(M), n_rows, rp, kp, r0, r1, _p(out), out.shape[1], _stream()), 'hsk_knn_gram_i8')
+    return out
+
+
+def knn_select(C: torch.Tensor, rows: int, row0: int, deg: torch.Tensor, sqrt_deg: Optional[torch.Tensor],
+               deg_alpha: Optional[torch.Tensor], deg_1m_alpha: Optional[torch.Tensor], kind: str, alpha: float,
+               beta: float, shrinkage: float, k: int):
+    """(idx int32 [rows, k], val fp64 [rows, k], len int32 [rows]) of the count block C (rows of C = entities row0...)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    if kind not in KNN_KINDS:
+        raise ValueError(f'unknown similarity {kind!r} (one of {sorted(KNN_KINDS)})')
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f'k = {k} outside [1, {KNN_MAX_K}]')
+    _chk(C, torch.int32, 'C')
+    n = deg.numel()
+    _chk(deg, torch.int64, 'deg', (n,))
+    for name, t in (('sqrt_deg', sqrt_deg), ('deg_alpha', deg_alpha), ('deg_1m_alpha', deg_1m_alpha)):
+        _chk(t, torch.float64, name, (n,), optional=True)
+    dev = C.device
+    idx = torch.empty((rows, k), dtype=torch.int32, device=dev)
+    val = torch.empty((rows, k), dtype=torch.float64, device=dev)
+    ln = torch.empty(rows, dtype=torch.int32, device=dev)
+    _lib.check(lib.hsk_knn_select(_p(C), rows, n, C.shape[1], row0, _p(deg), _p(sqrt_deg), _p(deg_alpha),
+                                  _p(deg_1m_alpha), KNN_KINDS[kind], float(alpha or 0.), float(beta or 0.),
+                                  float(shrinkage), k, _p(idx), _p(val), _p(ln), _stream()), 'hsk_knn_select')
+    return idx, val, ln
+
+
+def knn_score_rows(users: torch.Tensor, a_csr, b_csr, n_cols: int, window: int = 4096, excl=None,
+                   out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [R, n_cols]: row q = sum over A-row users[q] (stored order) of w_a * B-row.  a_csr / b_csr:
+    (indptr int64, indices int32, vals fp64 or None, n_rows); excl: (indptr, indices) -> those columns -inf."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(users, torch.int64, 'users')
+    R = users.numel()
+    (ap, ai, av, an), (bp, bi, bv, bn) = a_csr, b_csr
+    for name, (p, i, v, nr) in (('a', a_csr), ('b', b_csr)):
+        _chk(p, torch.int64, f'{name}_indptr', (nr + 1,))
+        _chk(i, torch.int32, f'{name}_indices')
+        _chk(v, torch.float64, f'{name}_vals', (i.numel(),), optional=True)
+    ep, ei = excl if excl is not None else (None, None)
+    if excl is not None:
+        _chk(ep, torch.int64, 'excl_indptr')
+        _chk(ei, torch.int32, 'excl_indices')
+    if out is None:
+        out = torch.empty((R, n_cols), dtype=torch.float64, device=users.device)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_cols:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_cols})')
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    window = max(1, min(int(window), KNN_MAX_WINDOW))
+    _lib.check(lib.hsk_knn_score_rows(_p(users), R, an, _p(ap), _p(ai), _p(av), bn, _p(bp), _p(bi), _p(bv), n_cols,
+                                      window, _p(ep), _p(ei), _p(out), out.shape[1], _p(status), _stream()),
+               'hsk_knn_score_rows')
+    return out
+
+
+def knn_topk_rows(scores: torch.Tensor, k: int, n_cols: Optional[int] = None):
+    """(values fp64 [R, k], ids int32 [R, k]) of each row's k largest, ties to the lower index."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(scores, torch.float64, 'scores')
+    R, ld = scores.shape
+    n_cols = ld if n_cols is None else n_cols
+    vals = torch.empty((R, k), dtype=torch.float64, device=scores.device)
+    ids = torch.empty((R, k), dtype=torch.int32, device=scores.device)
+    _lib.check(lib.hsk_knn_topk_rows(_p(scores), R, n_cols, ld, k, _p(vals), _p(ids), _stream()), 'hsk_knn_topk_rows')
+    return vals, ids

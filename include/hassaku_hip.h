@@ -640,6 +640,64 @@ int hsk_rank_metrics(const int32_t* topk_idx, int64_t n_rows, int64_t k_max,
                      const int64_t* label_indptr, const int32_t* label_indices,
                      const int32_t* ks, int32_t n_ks, float* out, hsk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ItemKNN / UserKNN (algorithms/knn_algs.py:13-140, utilities/similarities.py:18-111)
+ * ------------------------------------------------------------------------------------------ */
+
+/* similarity kinds (SimilarityFunctionEnum, utilities/similarities.py:105-110) */
+enum {
+  HSK_KNN_COSINE = 0,            /* c / (sqrt(dr) sqrt(dc))                      similarities.py:76-83 */
+  HSK_KNN_JACCARD = 1,           /* c / (dr + dc - c)                            similarities.py:64-73 */
+  HSK_KNN_SORENSEN_DICE = 2,     /* (c / (dr + dc)) * 2                          similarities.py:86-94 */
+  HSK_KNN_ASYMMETRIC_COSINE = 3, /* c / (dr^alpha dc^(1-alpha))                  similarities.py:97-108 */
+  HSK_KNN_TVERSKY = 4            /* c / (c + alpha (dr - c) + beta (dc - c))     similarities.py:111-121 */
+};
+#define HSK_KNN_MAX_K 1024        /* neighbours per entity and evaluation cut-off */
+#define HSK_KNN_MAX_WINDOW 20480  /* fp64 accumulators of one scoring wave (160 KiB of LDS) */
+
+/* padded shape of the int8 entity operand: rows_pad = n_rows rounded up to 128, k_pad = n_cols rounded up to 64
+ * (host pointers).  The operand takes rows_pad * k_pad bytes. */
+int hsk_knn_pack_dims(int64_t n_rows, int64_t n_cols, int64_t* rows_pad, int64_t* k_pad);
+
+/* binary CSR [n_rows, n_cols] (indices int32, sorted or not) -> dense int8 M [rows_pad, k_pad], zero padded: the
+ * entity matrix of compute_similarity_top_k (knn_algs.py:115 passes X, :133 passes X^T). */
+int hsk_knn_pack_i8(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                    int64_t rows_pad, int64_t k_pad, int8_t* out, hsk_stream_t stream);
+
+/* co-occurrence counts of a row block: C[r - r0, c] = sum_k M[r, k] M[c, k] (int32, exact) for r in [r0, r1),
+ * c in [0, n_rows); C has leading dimension ldc >= n_rows; r0 a multiple of 128.  Replaces `sub_mtx @ matrix.T`
+ * (similarities.py:67,79,...; the reference's int16 counts wrap above 32 767, these do not). */
+int hsk_knn_gram_i8(const int8_t* M, int64_t n_rows, int64_t rows_pad, int64_t k_pad, int64_t r0, int64_t r1,
+                    int32_t* C, int64_t ldc, hsk_stream_t stream);
+
+/* similarity + neighbours of a count block (similarities.py:18-61 and the kind's function): row i of C is entity
+ * row0 + i.  For every c with C[i, c] > 0 and c != row0 + i the fp64 similarity of `kind` is computed in the
+ * reference's operation order, then multiplied by C / (C + shrinkage); the k <= HSK_KNN_MAX_K largest are written
+ * in order (value desc, index asc): out_idx / out_val [rows, k], out_len [rows] (slots past out_len: -1 / 0).
+ * deg int64 [n]; sqrt_deg (cosine), deg_alpha and deg_1m_alpha (asymmetric cosine) fp64 [n], else may be NULL. */
+int hsk_knn_select(const int32_t* C, int64_t rows, int64_t n, int64_t ldc, int64_t row0, const int64_t* deg,
+                   const double* sqrt_deg, const double* deg_alpha, const double* deg_1m_alpha, int32_t kind,
+                   double alpha, double beta, double shrinkage, int64_t k, int32_t* out_idx, double* out_val,
+                   int32_t* out_len, hsk_stream_t stream);
+
+/* fp64 score rows of a sparse product (knn_algs.py:121 `sim_mtx @ matrix`, :139 `matrix @ sim_mtx.T`):
+ * out[q, j] = sum over the entries (r, w_a) of A-row users[q], in stored order, of w_a * B[r, j], each sum started
+ * at 0.0 and added in that order (scipy's csr @ csr order).  a_vals / b_vals NULL = weights 1.  One wave per (user,
+ * item window of `window` <= HSK_KNN_MAX_WINDOW columns).  If excl_indptr / excl_indices (CSR over the same user ids)
+ * are given, the user's excluded columns are set to -inf (eval/eval.py:222-236).  Out-of-range user ids set
+ * HSK_STATUS_BAD_INDEX in *status and read row 0. */
+int hsk_knn_score_rows(const int64_t* users, int64_t n_users, int64_t n_a_rows, const int64_t* a_indptr,
+                       const int32_t* a_indices, const double* a_vals, int64_t n_b_rows, const int64_t* b_indptr,
+                       const int32_t* b_indices, const double* b_vals, int64_t n_cols, int64_t window,
+                       const int64_t* excl_indptr, const int32_t* excl_indices, double* out, int64_t ld,
+                       int32_t* status, hsk_stream_t stream);
+
+/* fp64 top-k of each row of a dense [rows, n_cols] matrix (leading dimension ld), k <= HSK_KNN_MAX_K, order
+ * (value desc, index asc); ids int32 (the input of hsk_rank_metrics).  Replaces torch.topk on the masked
+ * float64 predictions (eval/eval.py:63). */
+int hsk_knn_topk_rows(const double* scores, int64_t rows, int64_t n_cols, int64_t ld, int64_t k, double* out_vals,
+                      int32_t* out_idx, hsk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
