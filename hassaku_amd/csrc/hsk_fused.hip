@@ -1770,6 +1770,14 @@ extern "C" int hsk_bprmf_train_steps(hsk_bprmf_state* st, const int64_t* order, 
     aux->tail_count = 0;
     return HSK_OK;
   }
+  if (st->aux && n_steps > 0) {
+    // not a pipelined run: batches an earlier pipelined run prepared for its tail hint (the pipeline switched off since,
+    // another batch size now) still claim their users in the owner maps of the buffer sets the replayed graphs are about
+    // to reuse -- give them back first, as the single-step paths and the flush do
+    int rc = hsk_check_state(st);
+    if (rc) return rc;
+    if ((rc = hsk_pipe_reset(st, hsk_carve_st(st), (hipStream_t)stream_))) return rc;
+  }
   const int64_t chunk_max = hsk_graph_chunk(st);
   if (chunk_max >= 2 && n_steps >= chunk_max) {
     int rc = hsk_check_state(st);
