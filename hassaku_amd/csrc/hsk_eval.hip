@@ -263,81 +263,79 @@ void hsk_eval_split_planes16(const float* src, const int64_t* idx, long long row
 }
 
 // ---------------------------------------------------------------------------------------------
-// Form 2: two fp16 pieces per operand (hsk_gemm_wide_h2.h).  The pre-pass first takes the largest finite |x| of the rows
-// it is about to cut -- those and no others: an item shard's table may be nothing but the shard (include/hassaku_hip.h).
-// A power-of-two scale changes no piece that stays a normal fp16, so shards of one catalogue (different maxima) agree
-// except in elements below 2^-17 of a maximum -- then writes hi / lo at the scale that puts that maximum in [2^14, 2^15),
-// laid out [Dp / 16 k-tiles][2 pieces][n_pad rows][16]: one (k-tile, piece) image of a 256-row block is 8 KB of
-// consecutive bytes.  The GEMM undoes both scales with one exact multiplication.
+// Form 2: two fp16 pieces per operand (hsk_gemm_wide_h2.h).  The pre-pass takes the largest finite |x| of EVERY ROW it is
+// about to cut and writes hi / lo of that row at the power-of-two scale that puts the row's own maximum in [2^14, 2^15)
+// -- a row's pieces depend on nothing but the row: a quiet row beside a loud one keeps all its bits, and shards of one
+// catalogue, an item range and the whole catalogue cut the same row into the same pieces (bit-equal scores) -- laid out
+// [Dp / 16 k-tiles][2 pieces][n_pad rows][16]: one (k-tile, piece) image of a 256-row block is 8 KB of consecutive bytes.
+// inv[r] = 2^-e_r (1 for an all-zero, an all-non-finite and a padding row); the GEMMs undo both scales with one exact
+// multiplication by inv_a[row] * inv_b[col] per score.
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 hsk_f16x4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void k_absmax_rows(const float* __restrict__ src, const int64_t* __restrict__ idx,
-                                                     long long row0, long long n_src_rows, long long n_rows, int D,
-                                                     uint32_t* __restrict__ out) {
-  const int per_row = D / 4;
-  const long long total = n_rows * per_row;
-  float m = 0.f;
-  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
-    const long long r = t / per_row;
-    const int k = (int)(t - r * per_row) * 4;
+// One wave per (padded) row, four rows per workgroup: the row's largest finite |x|, then its pieces -- one pass over the
+// table where a table-wide scale needed two.  Rows of up to 512 elements stay in registers between the two (both loads in
+// flight together); longer ones are read again, out of the cache the first read filled.
+__global__ __launch_bounds__(256) void k_split_planes_h2(const float* __restrict__ src, const int64_t* __restrict__ idx,
+                                                         long long row0, long long n_src_rows, int n_valid, int n_pad, int D,
+                                                         int Dp, float* __restrict__ inv, _Float16* __restrict__ planes) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_pad) return;
+  const float4* row = nullptr;   // (padding rows: zeros at scale 1)
+  if (r < n_valid) {
     long long sr = idx ? idx[r] : row0 + r;
-    if (sr < 0 || sr >= n_src_rows) sr = idx ? 0 : row0;   // (a bad index is reported by the scoring kernel)
-    const float4 x = *reinterpret_cast<const float4*>(src + sr * (long long)D + k);
+    if (sr < 0 || sr >= n_src_rows) sr = 0;   // (a bad index is reported by the scoring kernel)
+    row = reinterpret_cast<const float4*>(src + sr * (long long)D);
+  }
+  const int nv = D / 4;
+  const bool in_regs = nv <= 128;
+  float4 held[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+  float m = 0.f;
+  auto take = [&](const float4& x) {
     const float v[4] = {fabsf(x.x), fabsf(x.y), fabsf(x.z), fabsf(x.w)};
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (v[e] > m && v[e] < INFINITY) m = v[e];   // (NaN and inf do not take part)
+    for (int q = 0; q < 4; ++q)
+      if (v[q] > m && v[q] < INFINITY) m = v[q];   // (NaN and inf do not take part)
+  };
+  if (row && in_regs) {
+    if (lane < nv) held[0] = row[lane];
+    if (lane + 64 < nv) held[1] = row[lane + 64];
+    take(held[0]);
+    take(held[1]);
+  } else if (row) {
+    for (int c = lane; c < nv; c += 64) take(row[c]);
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
-  __shared__ float wmax[4];
-  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {   // one atomic per workgroup (8192 of them on one word took 70 us of a 10 us kernel)
-    m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-    if (m > 0.f) atomicMax(out, __float_as_uint(m));   // non-negative floats order like their bits
-  }
-}
-
-__global__ __launch_bounds__(256) void k_split_planes_h2(const float* __restrict__ src, const int64_t* __restrict__ idx,
-                                                         long long row0, long long n_src_rows, int n_valid, int n_pad, int D,
-                                                         int Dp, const uint32_t* __restrict__ amax,
-                                                         _Float16* __restrict__ planes) {
-  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-  const int per_row = Dp / 4;
-  const long long r = t / per_row;
-  const int k = (int)(t - r * per_row) * 4;
-  if (r >= n_pad) return;
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-  if (r < n_valid && k < D) {
-    long long sr = idx ? idx[r] : row0 + r;
-    if (sr < 0 || sr >= n_src_rows) sr = 0;   // (a bad index is reported by the scoring kernel)
-    const float4 x = *reinterpret_cast<const float4*>(src + sr * (long long)D + k);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-  }
-  const int e = hsk_h2_scale_exp(__uint_as_float(amax[0]));
-  hsk_f16x4 hi, lo;
+  const int e = hsk_h2_scale_exp(m);
+  if (lane == 0) inv[r] = ldexpf(1.f, -e);
+  for (int c = lane; c < Dp / 4; c += 64) {
+    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (in_regs) x = c < 64 ? held[0] : held[1];   // (Dp <= 512: c < 128)
+    else if (row && c < nv) x = row[c];
+    const float v[4] = {x.x, x.y, x.z, x.w};
+    hsk_f16x4 hi, lo;
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    _Float16 a, b;
-    hsk_split_h2(v[q], e, a, b);
-    hi[q] = a; lo[q] = b;
+    for (int q = 0; q < 4; ++q) {
+      _Float16 a, b;
+      hsk_split_h2(v[q], e, a, b);
+      hi[q] = a; lo[q] = b;
+    }
+    const int k = 4 * c;
+    _Float16* dst = planes + ((long long)(k / 16) * 2 * n_pad + r) * 16 + (k % 16);
+    *reinterpret_cast<hsk_f16x4*>(dst) = hi;
+    *reinterpret_cast<hsk_f16x4*>(dst + (long long)n_pad * 16) = lo;
   }
-  _Float16* dst = planes + ((long long)(k / 16) * 2 * n_pad + r) * 16 + (k % 16);
-  *reinterpret_cast<hsk_f16x4*>(dst) = hi;
-  *reinterpret_cast<hsk_f16x4*>(dst + (long long)n_pad * 16) = lo;
 }
 
-// (also used by hsk_eval_fused.hip)  planes: 4 * n_pad * Dp bytes; amax: one zeroed word the call keeps for the GEMM to read
+// (also used by hsk_eval_fused.hip)  planes: 4 * n_pad * Dp bytes; inv: n_pad floats the call keeps for the GEMM to read
+// (hsk_h2_inv_scales: they live behind the planes, in the third of the operand's region that form 2 leaves unused)
 void hsk_eval_split_planes_h2(const float* src, const int64_t* idx, long long row0, long long n_src_rows, int n_valid,
-                              int n_pad, int D, uint32_t* amax, void* planes, hipStream_t stream) {
+                              int n_pad, int D, float* inv, void* planes, hipStream_t stream) {
   const int Dp = (int)hsk_align_up(D, GEMM_BK);
-  const long long work = (long long)n_valid * (D / 4);
-  const unsigned nb = (unsigned)std::min<long long>(1024, std::max<long long>(1, hsk_ceil_div(work, 256 * 8)));
-  k_absmax_rows<<<nb, 256, 0, stream>>>(src, idx, row0, n_src_rows, n_valid, D, amax);
-  const unsigned nblk = (unsigned)hsk_ceil_div((long long)n_pad * (Dp / 4), 256);
-  k_split_planes_h2<<<nblk, 256, 0, stream>>>(src, idx, row0, n_src_rows, n_valid, n_pad, D, Dp, amax, (_Float16*)planes);
+  k_split_planes_h2<<<(unsigned)hsk_ceil_div(n_pad, 4), 256, 0, stream>>>(src, idx, row0, n_src_rows, n_valid, n_pad, D, Dp, inv,
+                                                                          (_Float16*)planes);
 }
 
 typedef unsigned hsk_vu32x4 __attribute__((ext_vector_type(4)));   // (an array of HIP's uint4 structs ends up in scratch)
@@ -553,13 +551,15 @@ __global__ __launch_bounds__(256, 2) void k_score_gemm_x3(const float* __restric
 // Epilogue of the 256 x 256 score GEMMs, through LDS.  One workgroup per CU: nothing covers this phase, so its length
 // counts in full -- and as dword-per-lane stores (256 per wave, every 128-byte piece split over two cache lines when the
 // row stride is not a multiple of 32 floats: item_count = 10 677) it took about a quarter of the kernel at the ml10m
-// shape.  Per band of 32 rows the four waves put their accumulators into LDS -- scaled by cs (form 2; exact), biases added
+// shape.  Per band of 32 rows the four waves put their accumulators into LDS -- scaled by inv_a[row] * inv_b[col] (form 2;
+// a power of two: exact), biases added
 // in the reference's order (+= u_bias, += i_bias, += global_bias), each row shifted by its own misalignment
 // (row * item_count + n0) mod 4 so that 16-byte pieces of LDS are 16-byte pieces of global memory -- and every wave then
 // writes 16 whole rows of the band's 256 columns with one ds_read_b128 + one global_store_dwordx4 per lane and row; the
 // ragged ends go out as dwords.  st: 2 x 32 rows of 264 floats = 67.6 KB of the (dead) operand stages.
 template <bool SCALE>
-__device__ __forceinline__ void hsk_wide_store_scores(const hsk_w_f32x16 (&acc)[4][4], float* st, float cs,
+__device__ __forceinline__ void hsk_wide_store_scores(const hsk_w_f32x16 (&acc)[4][4], float* st,
+                                                      const float* __restrict__ inv_a, const float* __restrict__ inv_b,
                                                       const float* __restrict__ Ib, const float* __restrict__ Ub,
                                                       const float* __restrict__ gb, int n_users,
                                                       const int64_t* __restrict__ u_idx, int n_rows, long long item_begin,
@@ -570,11 +570,12 @@ __device__ __forceinline__ void hsk_wide_store_scores(const hsk_w_f32x16 (&acc)[
   const float gbv = gb ? gb[0] : 0.f;
   const int ncols = min(256, item_count - n0);       // valid columns of this block
   const int ic3 = item_count & 3;
-  float ibv[TN];
+  float ibv[TN], sbv[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int col = n0 + wn * WN + j * 32 + r32;
     ibv[j] = (Ib && col < item_count) ? Ib[item_begin + col] : 0.f;
+    sbv[j] = SCALE ? inv_b[col] : 1.f;               // (col < the planes' padded row count)
   }
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
@@ -592,11 +593,12 @@ __device__ __forceinline__ void hsk_wide_store_scores(const hsk_w_f32x16 (&acc)[
         }
         if (Ub) ub = Ub[uu];
       }
+      const float sa = SCALE ? inv_a[row] : 1.f;     // (row < the planes' padded row count)
       const int shift = ((row & 3) * ic3) & 3;       // (row * item_count + n0) mod 4, n0 a multiple of 256
       float* dst = st + (wm * 32 + rloc) * LDR + wn * WN + r32 + shift;
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        float o = SCALE ? acc[i][j][q] * cs : acc[i][j][q];
+        float o = SCALE ? acc[i][j][q] * (sa * sbv[j]) : acc[i][j][q];
         if (Ub) o += ub;
         if (Ib) o += ibv[j];
         if (gb) o += gbv;
@@ -660,12 +662,12 @@ __global__ __launch_bounds__(256, 1) void k_score_gemm_x3_wide(const float* __re
   hsk_wide_load(stg, a0 + (NT > 1 ? a_step : 0), b0 + (NT > 1 ? b_step : 0), tid);   // k-tile 1 -> registers
   __syncthreads();
   hsk_wide_kloop(acc, stg, As, Bs, a0, b0, a_step, b_step, NT, tid, wm, wn, r32, h);
-  hsk_wide_store_scores<false>(acc, reinterpret_cast<float*>(wlds), 1.f, Ib, Ub, gb, n_users, u_idx, n_rows, item_begin, item_count,
+  hsk_wide_store_scores<false>(acc, reinterpret_cast<float*>(wlds), nullptr, nullptr, Ib, Ub, gb, n_users, u_idx, n_rows, item_begin, item_count,
                                C, status, m0, n0, lane, wm, wn, r32, h);
 }
 
 // The same on two fp16 pieces per operand, three products (hsk_gemm_wide_h2.h; planes from hsk_eval_split_planes_h2).
-// amax[0] / amax[1]: the largest |x| the user / item pieces were scaled by.
+// inv_a [a_rows] / inv_b [b_rows]: 2^-e of the scale 2^e every user / item row's pieces were cut at.
 __global__ __launch_bounds__(256, 1) void k_score_gemm_h2_wide(const float* __restrict__ Ib, const float* __restrict__ Ub,
                                                                const float* __restrict__ gb, int n_users, int Dp,
                                                                const int64_t* __restrict__ u_idx, int n_rows,
@@ -673,7 +675,8 @@ __global__ __launch_bounds__(256, 1) void k_score_gemm_h2_wide(const float* __re
                                                                float* __restrict__ C, int32_t* status,
                                                                const _Float16* __restrict__ Apl,
                                                                const _Float16* __restrict__ Bpl, int a_rows, int b_rows,
-                                                               const uint32_t* __restrict__ amax) {
+                                                               const float* __restrict__ inv_a,
+                                                               const float* __restrict__ inv_b) {
   extern __shared__ __attribute__((aligned(16))) unsigned char hlds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -686,7 +689,6 @@ __global__ __launch_bounds__(256, 1) void k_score_gemm_h2_wide(const float* __re
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-  const float cs = ldexpf(1.f, -(hsk_h2_scale_exp(__uint_as_float(amax[0])) + hsk_h2_scale_exp(__uint_as_float(amax[1]))));
   hsk_h2_stage stg;
   const int NT = Dp / GEMM_H_BK;
   hsk_h2_load(stg, Apl, Bpl, a_rows, b_rows, m0, n0, 0, tid);                  // k-step 0 -> LDS stage 0
@@ -694,7 +696,7 @@ __global__ __launch_bounds__(256, 1) void k_score_gemm_h2_wide(const float* __re
   hsk_h2_load(stg, Apl, Bpl, a_rows, b_rows, m0, n0, NT > 1 ? 1 : 0, tid);     // k-step 1 -> registers
   __syncthreads();
   hsk_h2_kloop(acc, stg, hlds, Apl, Bpl, a_rows, b_rows, m0, n0, NT, tid, wm, wn, r32, h);
-  hsk_wide_store_scores<true>(acc, reinterpret_cast<float*>(hlds), cs, Ib, Ub, gb, n_users, u_idx, n_rows, item_begin, item_count,
+  hsk_wide_store_scores<true>(acc, reinterpret_cast<float*>(hlds), inv_a, inv_b, Ib, Ub, gb, n_users, u_idx, n_rows, item_begin, item_count,
                               C, status, m0, n0, lane, wm, wn, r32, h);
 }
 
@@ -1155,15 +1157,17 @@ __global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ va
     if (c < total) {
       const int p = c / k, j = c - p * k;
       const long long src = ((long long)p * rows + r) * k + j;
-      v = ((unsigned long long)hsk_f2key(vals[src]) << 32) | (uint32_t)(~(uint32_t)idx[src]);
+      // an entry with id 0x7fffffff is a pad (a list shorter than k): key 0, below everything real -- also below a NaN
+      // score with its sign bit set, whose key lies under -inf's (as k_fused_merge of hsk_eval_fused.hip)
+      if (idx[src] != 0x7fffffff) v = ((unsigned long long)hsk_f2key(vals[src]) << 32) | (uint32_t)(~(uint32_t)idx[src]);
     }
     cand[c] = v;
   }
   hsk_bitonic_desc(cand, npad);
   for (int c = threadIdx.x; c < k; c += 256) {
     const unsigned long long v = cand[c];
-    out_vals[(long long)r * k + c] = hsk_key2f((uint32_t)(v >> 32));
-    out_idx[(long long)r * k + c] = (int32_t)(~(uint32_t)v);
+    out_vals[(long long)r * k + c] = v ? hsk_key2f((uint32_t)(v >> 32)) : -INFINITY;   // (fewer than k real entries: pads)
+    out_idx[(long long)r * k + c] = v ? (int32_t)(~(uint32_t)v) : 0x7fffffff;
   }
 }
 
@@ -1308,14 +1312,14 @@ extern "C" int hsk_mf_eval_topk_planes(const float* user_emb, const float* item_
     const int64_t Dp = hsk_align_up(dim, GEMM_BK);
     const int a_rows = (int)hsk_align_up(n_rows, GEMM_W_BM), b_rows = (int)hsk_align_up(item_count, GEMM_W_BN);
     if (x3 == 2) {
-      // form 2: fp16 pairs (4 of the region's 6 bytes per element; the two scale words sit in its last 256 bytes),
-      // the 256 x 256 kernel whatever the shape
+      // form 2: fp16 pairs (4 of the region's 6 bytes per element; every row's scale word sits behind its operand's
+      // pieces, in the 2 bytes per element they leave), the 256 x 256 kernel whatever the shape
       _Float16* Ah = (_Float16*)planes_ws;
       _Float16* Bh = (_Float16*)((char*)planes_ws + hsk_align_up(6 * (int64_t)a_rows * Dp, 256));
-      uint32_t* amax = (uint32_t*)((char*)planes_ws + hsk_mf_eval_planes_bytes(n_rows, item_count, dim) - 256);
-      HSK_HIP(hipMemsetAsync(amax, 0, 8, stream));
-      hsk_eval_split_planes_h2(user_emb, u_idx, 0, n_users, (int)n_rows, a_rows, (int)dim, amax, Ah, stream);
-      hsk_eval_split_planes_h2(item_emb, nullptr, item_begin, n_items, (int)item_count, b_rows, (int)dim, amax + 1, Bh, stream);
+      float* inv_a = hsk_h2_inv_scales(Ah, a_rows, Dp);
+      float* inv_b = hsk_h2_inv_scales(Bh, b_rows, Dp);
+      hsk_eval_split_planes_h2(user_emb, u_idx, 0, n_users, (int)n_rows, a_rows, (int)dim, inv_a, Ah, stream);
+      hsk_eval_split_planes_h2(item_emb, nullptr, item_begin, n_items, (int)item_count, b_rows, (int)dim, inv_b, Bh, stream);
       HSK_LAUNCH_CHECK();
       int rc = hsk_eval_set_wide_lds();
       if (rc) return rc;
@@ -1323,7 +1327,7 @@ extern "C" int hsk_mf_eval_topk_planes(const float* user_emb, const float* item_
       k_score_gemm_h2_wide<<<wgrid, 256, GEMM_H_LDS_BYTES, stream>>>(item_bias, user_bias, global_bias, (int)n_users, (int)Dp,
                                                                      u_idx, (int)n_rows, (long long)item_begin,
                                                                      (int)item_count, scores_ws, status, Ah, Bh, a_rows, b_rows,
-                                                                     amax);
+                                                                     inv_a, inv_b);
     } else {
     __bf16* Apl = (__bf16*)planes_ws;
     __bf16* Bpl = (__bf16*)((char*)planes_ws + hsk_align_up(6 * (int64_t)a_rows * Dp, 256));
@@ -1384,15 +1388,17 @@ __global__ __launch_bounds__(256) void k_seed_keys(const float* __restrict__ val
 int hsk_eval_seed_thresholds(const float* item_bias, const float* user_bias, const float* global_bias, int n_users, int Dp,
                              const int64_t* u_idx, int n_rows, long long item_begin, int sample_count,
                              const int64_t* excl_indptr, const int32_t* excl_indices, int k, const void* Apl,
-                             const void* Bpl, int a_rows, int b_rows, const uint32_t* amax, float* scores_ws, float* vals_ws,
-                             int32_t* idx_ws, uint32_t* gthr, int32_t* status, hipStream_t stream) {
+                             const void* Bpl, int a_rows, int b_rows, const float* inv_a, const float* inv_b,
+                             float* scores_ws, float* vals_ws, int32_t* idx_ws, uint32_t* gthr, int32_t* status,
+                             hipStream_t stream) {
   int rc0 = hsk_eval_set_wide_lds();
   if (rc0) return rc0;
   dim3 wgrid((unsigned)hsk_ceil_div(sample_count, GEMM_W_BN), (unsigned)hsk_ceil_div(n_rows, GEMM_W_BM));
-  if (amax)   // form 2: the pieces are fp16 pairs
+  if (inv_a)   // form 2: the pieces are fp16 pairs
     k_score_gemm_h2_wide<<<wgrid, 256, GEMM_H_LDS_BYTES, stream>>>(item_bias, user_bias, global_bias, n_users, Dp, u_idx, n_rows,
                                                                    item_begin, sample_count, scores_ws, status,
-                                                                   (const _Float16*)Apl, (const _Float16*)Bpl, a_rows, b_rows, amax);
+                                                                   (const _Float16*)Apl, (const _Float16*)Bpl, a_rows, b_rows, inv_a,
+                                                                   inv_b);
   else
     k_score_gemm_x3_wide<<<wgrid, 256, GEMM_W_LDS_BYTES, stream>>>(item_bias, user_bias, global_bias, n_users, Dp, u_idx, n_rows,
                                                                    item_begin, sample_count, scores_ws, status,

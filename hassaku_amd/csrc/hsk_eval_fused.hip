@@ -536,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void k_score_topk(const float* __restrict__
 #define FGW_CAP 640            // candidates a row can hold between two compactions: TRIG + one whole tile of 256 columns
 #define FGW_TRIG 384
 #define FGW_Q 1536             // queue entries per wave: drained when it holds > 512 (a band adds at most 16 sites x 64 lanes)
-#define FGW_STATE_BYTES (3 * 256 * 4 + 256 * 8 * 4)   // thr, cnt, ubias [256] + emask [256][8]
+#define FGW_STATE_BYTES (4 * 256 * 4 + 256 * 8 * 4)   // thr, cnt, ubias, inv_a [256] + emask [256][8]
 #define FGW_LDS_BYTES (GEMM_W_LDS_BYTES + FGW_STATE_BYTES)
 #define FGW_H2_LDS_BYTES (GEMM_H_LDS_BYTES + FGW_STATE_BYTES)   // on the fp16-pair core (hsk_gemm_wide_h2.h)
 static_assert(FGW_LDS_BYTES <= 160 * 1024, "LDS of k_score_topk_wide");
@@ -545,8 +545,8 @@ static_assert(4 * FGW_Q * 20 + 4 * 256 * 4 + 4 * HSK_SEL_KMAX * 8 <= GEMM_H_LDS_
 
 // HAS_IB: item bias present; EXTRA: a user and / or global bias as well (the additions follow the reference's order and
 // are left out, not replaced by + 0, where a bias is absent: -0 + 0 would change a sign bit the materialised path keeps)
-// H2: the fp16-pair / three-product core (form 2 of hsk_eval_set_arith): Apl / Bpl are its planes, amax the two maxima the
-// planes were scaled by; every score is the accumulator times 2^-(e_a + e_b), exact
+// H2: the fp16-pair / three-product core (form 2 of hsk_eval_set_arith): Apl / Bpl are its planes, inv_a / inv_b the rows'
+// inverse scales 2^-e (hsk_gemm_wide_h2.h); every score is the accumulator times inv_a[row] * inv_b[col], exact
 template <bool HAS_IB, bool EXTRA, bool H2 = false>
 __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
     const float* __restrict__ Ib, const float* __restrict__ Ub, const float* __restrict__ gb, int n_users, int Dp,
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
     const int64_t* __restrict__ excl_indptr, const int32_t* __restrict__ excl_indices, int k, int n_splits,
     unsigned long long* __restrict__ cand_ws, float* __restrict__ part_vals, int32_t* __restrict__ part_idx,
     int32_t* status, const void* __restrict__ Apl_, const void* __restrict__ Bpl_, int a_rows, int b_rows,
-    uint32_t* __restrict__ gthr, int dbg, int pw, const uint32_t* __restrict__ amax) {
+    uint32_t* __restrict__ gthr, int dbg, int pw, const float* __restrict__ inv_a, const float* __restrict__ inv_b) {
   // pw: entries per row of this split's partial list: k (one split: the final, sorted list) or HSK_SEL_KMAX (several:
   // k_fused_merge sorts the union anyway, so a row that ends with <= pw survivors is handed over as it is -- no select)
   // gthr [n_rows] (zero-initialised keys): the best threshold any split has reached for the row.  A split's k-th best score
@@ -573,12 +573,11 @@ __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
   const _Float16* __restrict__ Bh = reinterpret_cast<const _Float16*>(Bpl_);
   unsigned char* hlds = reinterpret_cast<unsigned char*>(wlds);
   unsigned char* state = reinterpret_cast<unsigned char*>(wlds) + (H2 ? GEMM_H_LDS_BYTES : GEMM_W_LDS_BYTES);
-  float cs = 1.f;
-  if constexpr (H2) cs = ldexpf(1.f, -(hsk_h2_scale_exp(__uint_as_float(amax[0])) + hsk_h2_scale_exp(__uint_as_float(amax[1]))));
   float* thr = reinterpret_cast<float*>(state);               // [256] current k-th best score of the row
   int* cnt = reinterpret_cast<int*>(state + 1024);            // [256] candidates the row holds
   float* ubias = reinterpret_cast<float*>(state + 2048);      // [256]
-  uint32_t* emask = reinterpret_cast<uint32_t*>(state + 3072);   // [256][8] exclusion bits of the current tile
+  float* sa = reinterpret_cast<float*>(state + 3072);         // [256] H2: the row's inverse scale
+  uint32_t* emask = reinterpret_cast<uint32_t*>(state + 4096);   // [256][8] exclusion bits of the current tile
   // during the epilogue / the compactions the operand stages are idle: queues and select scratch live there
   unsigned char* idle = reinterpret_cast<unsigned char*>(wlds);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -614,6 +613,7 @@ __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
       u = (int)uu;
     }
     ubias[tid] = Ub ? Ub[u] : 0.f;
+    sa[tid] = H2 ? inv_a[r] : 1.f;   // (r < a_rows: the planes' padded row count)
     // rows past n_rows: nothing ever passes (and nothing ever lowers it); the others start from the seeded lower bound
     const uint32_t k0 = (gthr && r < n_rows) ? gthr[r] : 0u;   // (key 0: no bound yet)
     thr[tid] = r < n_rows ? (k0 ? fg_key2f(k0) : -INFINITY) : INFINITY;
@@ -636,6 +636,16 @@ __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
     }
   }
   const float gbv = gb ? gb[0] : 0.f;
+  if (t_lo >= t_hi) {   // a split past the last tile (tiles_per_split is rounded up): pads only, no operand is read
+    for (int rloc = tid; rloc < BM && m0 + rloc < n_rows; rloc += 256) {
+      const long long dst = ((long long)split * n_rows + m0 + rloc) * pw;
+      for (int j = 0; j < pw; ++j) {
+        part_vals[dst + j] = -INFINITY;
+        part_idx[dst + j] = 0x7fffffff;
+      }
+    }
+    return;
+  }
 
   constexpr int KPL = FGW_CAP / 64;   // keys per lane of a compaction
   // MSB-first radix select of the k-th largest key, 8 bits per pass.  Two things keep it to ~2 passes instead of 8: the
@@ -788,16 +798,18 @@ __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
     }
 
     // ---- epilogue: filter -> per-wave queue -> dense drain, band by band ---------------------------------------
-    float ibv[TN];
+    float ibv[TN], sbv[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int col = n0 + wn * 128 + j * 32 + r32;
       ibv[j] = (HAS_IB && col < item_count) ? Ib[item_begin + col] : 0.f;
+      sbv[j] = H2 ? inv_b[col] : 1.f;   // (col < b_rows)
     }
     // this lane's rows of band i: row_base + i * 32 + (q & 3) + 8 * (q >> 2) -- one base register, immediate offsets
     const int row_base = wm * 128 + 4 * h;
     const float* thr_b = thr + row_base;
     const float* ub_b = ubias + row_base;
+    const float* sa_b = sa + row_base;
     const int meta_base = row_base | ((wn * 128 + r32) << 16);
     int qn = 0;   // wave-uniform queue fill (carried across the bands: drained when it runs high, and at the tile's end)
     if (dbg & 1) {   // (timing experiments only: HSK_FUSED_DEBUG) keep the accumulators alive, select nothing
@@ -816,9 +828,10 @@ __global__ __launch_bounds__(256, 1) void k_score_topk_wide(
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         hsk_f32x4 o;
+        const float sar = H2 ? sa_b[i * 32 + (q & 3) + 8 * (q >> 2)] : 1.f;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          float x = H2 ? acc[i][j][q] * cs : acc[i][j][q];
+          float x = H2 ? acc[i][j][q] * (sar * sbv[j]) : acc[i][j][q];
           if (EXTRA) {   // reference order: += u_bias, += i_bias, += global_bias
             if (Ub) x += ub_b[i * 32 + (q & 3) + 8 * (q >> 2)];
             if (HAS_IB) x += ibv[j];
@@ -934,7 +947,9 @@ __global__ __launch_bounds__(256) void k_fused_merge(const float* __restrict__ v
     if (c < total) {
       const int p = c / pw, j = c - p * pw;
       const long long src = ((long long)p * rows + r) * pw + j;
-      v = ((unsigned long long)fg_f2key(vals[src]) << 32) | (uint32_t)(~(uint32_t)idx[src]);
+      // a pad (a list that ends early) is key 0, below everything real -- also below a NaN score with its sign bit set,
+      // whose key lies under -inf's: as (-inf, 0x7fffffff) the pads outranked such entries and came back as ids
+      if (idx[src] != 0x7fffffff) v = ((unsigned long long)fg_f2key(vals[src]) << 32) | (uint32_t)(~(uint32_t)idx[src]);
     }
     merge_keys[c] = v;
   }
@@ -956,8 +971,8 @@ __global__ __launch_bounds__(256) void k_fused_merge(const float* __restrict__ v
   __syncthreads();
   for (int c = threadIdx.x; c < k; c += 256) {
     const unsigned long long v = merge_keys[c];
-    out_vals[(long long)r * k + c] = fg_key2f((uint32_t)(v >> 32));
-    out_idx[(long long)r * k + c] = (int32_t)(~(uint32_t)v);
+    out_vals[(long long)r * k + c] = v ? fg_key2f((uint32_t)(v >> 32)) : -INFINITY;   // (fewer than k real entries: pads)
+    out_idx[(long long)r * k + c] = v ? (int32_t)(~(uint32_t)v) : 0x7fffffff;
   }
 }
 
@@ -967,11 +982,12 @@ void hsk_eval_split_planes(const float* src, const int64_t* idx, long long row0,
 int hsk_eval_seed_thresholds(const float* item_bias, const float* user_bias, const float* global_bias, int n_users, int Dp,
                              const int64_t* u_idx, int n_rows, long long item_begin, int sample_count,
                              const int64_t* excl_indptr, const int32_t* excl_indices, int k, const void* Apl,
-                             const void* Bpl, int a_rows, int b_rows, const uint32_t* amax, float* scores_ws, float* vals_ws,
-                             int32_t* idx_ws, uint32_t* gthr, int32_t* status, hipStream_t stream);   // hsk_eval.hip
-// form 2: fp16 pairs [k-tile of 16][piece][row][16] at the scale of the rows' largest |x| (hsk_gemm_wide_h2.h)
+                             const void* Bpl, int a_rows, int b_rows, const float* inv_a, const float* inv_b,
+                             float* scores_ws, float* vals_ws, int32_t* idx_ws, uint32_t* gthr, int32_t* status,
+                             hipStream_t stream);   // hsk_eval.hip
+// form 2: fp16 pairs [k-tile of 16][piece][row][16], every row at the scale of its own largest |x| (hsk_gemm_wide_h2.h)
 void hsk_eval_split_planes_h2(const float* src, const int64_t* idx, long long row0, long long n_src_rows, int n_valid,
-                              int n_pad, int D, uint32_t* amax, void* planes, hipStream_t stream);
+                              int n_pad, int D, float* inv, void* planes, hipStream_t stream);
 // ... laid out [k-tile of 16][row][piece][16]: what the 256 x 256 core reads
 void hsk_eval_split_planes16(const float* src, const int64_t* idx, long long row0, long long n_src_rows, int n_valid,
                              int n_pad, int D, void* planes, hipStream_t stream);
@@ -1102,12 +1118,12 @@ extern "C" int hsk_mf_eval_topk_fused(const float* user_emb, const float* item_e
       const int a_rows = (int)(row_blocks * GEMM_W_BM), b_rows = (int)(n_tiles * GEMM_W_BN);
       void* Apl = (char*)ws + need;
       void* Bpl = (char*)Apl + hsk_align_up(3 * (int64_t)a_rows * Dp * 2, 256);
-      // (form 2: fp16 pairs fill 4 of the regions' 6 bytes per element; the two scale words sit in the last 256 bytes)
-      uint32_t* amax = h2 ? (uint32_t*)((char*)Apl + hsk_fused_plane_bytes(n_rows, item_count, dim) - 256) : nullptr;
+      // (form 2: fp16 pairs fill 4 of the regions' 6 bytes per element; the rows' scale words sit behind them)
+      float* inv_a = h2 ? hsk_h2_inv_scales(Apl, a_rows, Dp) : nullptr;
+      float* inv_b = h2 ? hsk_h2_inv_scales(Bpl, b_rows, Dp) : nullptr;
       if (h2) {
-        HSK_HIP(hipMemsetAsync(amax, 0, 8, stream));
-        hsk_eval_split_planes_h2(user_emb, u_idx, 0, n_users, (int)n_rows, a_rows, (int)dim, amax, Apl, stream);
-        hsk_eval_split_planes_h2(item_emb, nullptr, item_begin, n_items, (int)item_count, b_rows, (int)dim, amax + 1, Bpl,
+        hsk_eval_split_planes_h2(user_emb, u_idx, 0, n_users, (int)n_rows, a_rows, (int)dim, inv_a, Apl, stream);
+        hsk_eval_split_planes_h2(item_emb, nullptr, item_begin, n_items, (int)item_count, b_rows, (int)dim, inv_b, Bpl,
                                  stream);
       } else {
         hsk_eval_split_planes16(user_emb, u_idx, 0, n_users, (int)n_rows, a_rows, (int)dim, Apl, stream);
@@ -1117,7 +1133,7 @@ extern "C" int hsk_mf_eval_topk_fused(const float* user_emb, const float* item_e
       if (seed_cols) {
         int src = hsk_eval_seed_thresholds(item_bias, user_bias, global_bias, (int)n_users, Dp, u_idx, (int)n_rows,
                                            (long long)item_begin, (int)seed_cols, excl_indptr, excl_indices, (int)k, Apl, Bpl,
-                                           a_rows, b_rows, amax, seed_scores, seed_vals, seed_idx, gthr, status, stream);
+                                           a_rows, b_rows, inv_a, inv_b, seed_scores, seed_vals, seed_idx, gthr, status, stream);
         if (src) return src;
       }
       static bool lds_set[64] = {};   // per device: the opt-in for > 64 KB of dynamic LDS is a per-device attribute
@@ -1139,7 +1155,7 @@ extern "C" int hsk_mf_eval_topk_fused(const float* user_emb, const float* item_e
   k_score_topk_wide<IB, EX, H><<<grid, 256, H ? FGW_H2_LDS_BYTES : FGW_LDS_BYTES, stream>>>(                            \
       item_bias, user_bias, global_bias, (int)n_users, Dp, u_idx, (int)n_rows, (long long)item_begin, (int)item_count, \
       tiles_per_split, excl_indptr, excl_indices, (int)k, SW, slab, SW == 1 ? out_vals : part_vals,                    \
-      SW == 1 ? out_idx : part_idx, status, Apl, Bpl, a_rows, b_rows, gthr, dbg, pw, amax)
+      SW == 1 ? out_idx : part_idx, status, Apl, Bpl, a_rows, b_rows, gthr, dbg, pw, inv_a, inv_b)
 #define HSK_TOPK_WIDE(IB, EX) do { if (h2) HSK_TOPK_WIDE_K(IB, EX, true); else HSK_TOPK_WIDE_K(IB, EX, false); } while (0)
       static const int dbg = getenv("HSK_FUSED_DEBUG") ? atoi(getenv("HSK_FUSED_DEBUG")) : 0;   // timing experiments
       const bool extra = user_bias || global_bias;

@@ -1,13 +1,16 @@
 // hsk_gemm_wide_h2.h -- the k loop of the 256 x 256 score GEMM on TWO fp16 pieces per operand, three products per block.
 //
-// x (fp32), scaled by a power of two s so that the table's largest |x| sits in [2^14, 2^15), is cut into hi = fp16(s x)
-// and lo = fp16(s x - hi): 11 + 11 significant bits, each cut exact in fp32; lo is a normal fp16 for every element within
-// 2^-18 of the table's maximum (below that it loses bits it no longer matters to keep: |error| <= 2^-40 of the maximum).
-// Of the four products per (a, b) pair the three of weight >= 2^-11 are kept -- a_lo b_hi, a_hi b_lo, a_hi b_hi, each a
-// v_mfma_f32_32x32x16_f16 into the same fp32 accumulator (an fp16 x fp16 product is exact in fp32); the dropped a_lo b_lo
-// and the pieces' own rounding are <= 2^-21 |a||b| per term -- measured below an fp32 GEMM's own rounding noise
-// (profiles/probes/gemm_f16x2.hip) -- at HALF the MFMAs of the three-piece bf16 form (hsk_gemm_wide.h) and 4 instead of 6
-// bytes per operand element through the L2s.  score = acc * 2^-(e_a + e_b), exact.
+// x (fp32), scaled by a power of two s so that the largest |x| of ITS ROW (a user's / an item's embedding) sits in
+// [2^14, 2^15), is cut into hi = fp16(s x) and lo = fp16(s x - hi): 11 + 11 significant bits, each cut exact in fp32; lo is
+// a normal fp16 for every element within 2^-18 of its row's maximum (below that it loses bits it no longer matters to
+// keep: |error| <= 2^-40 of the row's maximum, against a score whose natural scale sum |a||b| holds that maximum).  The
+// scale is per row, not per table: one runaway row (or one quiet one) changes nobody else's pieces, and a row's pieces do
+// not depend on which shard or item range it is scored in.  Of the four products per (a, b) pair the three of weight
+// >= 2^-11 are kept -- a_lo b_hi, a_hi b_lo, a_hi b_hi, each a v_mfma_f32_32x32x16_f16 into the same fp32 accumulator (an
+// fp16 x fp16 product is exact in fp32); the dropped a_lo b_lo and the pieces' own rounding are <= 2^-21 |a||b| per term
+// -- measured below an fp32 GEMM's own rounding noise (profiles/probes/gemm_f16x2.hip) -- at HALF the MFMAs of the
+// three-piece bf16 form (hsk_gemm_wide.h) and 4 instead of 6 bytes per operand element through the L2s.
+// score = acc * 2^-(e_row + e_col), exact.
 //
 // Same geometry as hsk_gemm_wide.h: a workgroup of four waves (one per SIMD) owns 256 x 256 outputs, wave (wm, wn) the
 // 128 x 128 block at (128 wm, 128 wn) in 4 x 4 accumulator tiles.  A k-step is 32 deep: two k16 tiles x two pieces =
@@ -29,8 +32,8 @@ typedef _Float16 hsk_w_f16x8 __attribute__((ext_vector_type(8)));
 #define GEMM_H_STAGE (2 * GEMM_H_OP_STAGE)       // A then B
 #define GEMM_H_LDS_BYTES (2 * GEMM_H_STAGE)      // 131 072
 
-// exponent e of the scale 2^e for a table whose largest finite |x| is amax: 2^e amax in [2^14, 2^15); clamped so that
-// 2^-(e_a + e_b) stays a normal fp32
+// exponent e of the scale 2^e for a row whose largest finite |x| is amax: 2^e amax in [2^14, 2^15); clamped so that
+// 2^-(e_a + e_b) stays a normal fp32.  No finite non-zero element: 0.
 __device__ __forceinline__ int hsk_h2_scale_exp(float amax) {
   if (!(amax > 0.f)) return 0;
   int e = 14 - ilogbf(amax);
@@ -42,6 +45,12 @@ __device__ __forceinline__ void hsk_split_h2(float x, int e, _Float16& hi, _Floa
   hi = (_Float16)xs;
   const float hf = (float)hi;
   lo = __builtin_isfinite(hf) ? (_Float16)(xs - hf) : (_Float16)0.f;
+}
+
+// where the rows' inverse scales (2^-e, one float per padded row) of an operand live: behind its pieces (4 of the 6 bytes
+// per element that the operand's region is sized for: form 1's three bf16 pieces)
+static inline float* hsk_h2_inv_scales(void* planes, long long rows, long long Dp) {
+  return reinterpret_cast<float*>(reinterpret_cast<char*>(planes) + 4 * rows * Dp);
 }
 
 struct hsk_h2_stage {

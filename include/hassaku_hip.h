@@ -362,10 +362,14 @@ int hsk_bprmf_last_batch(const hsk_bprmf_state* st, int64_t batch, int64_t n_col
                          int64_t* u_out, int64_t* i_out, hsk_stream_t stream);
 
 /* Arithmetic of the score GEMMs of hsk_mf_eval_topk[_planes] and hsk_mf_eval_topk_fused:
- *   2 (default)  every fp32 operand scaled by a power of two (its table's largest |x| -> [2^14, 2^15)) and cut into two fp16
- *                pieces, three fp16 MFMAs per product block on the 256 x 256 kernels -- error against float64 at or below
- *                that of an fp32 GEMM (<= 1e-6 of the largest score; pieces exact for every element within 2^-18 of the
- *                table's maximum), at half the MFMAs of form 1.  Taken wherever the call brings the pieces' scratch
+ *   2 (default)  every fp32 operand ROW (a user's / an item's embedding) scaled by a power of two of its own (the row's
+ *                largest finite |x| -> [2^14, 2^15)) and cut into two fp16 pieces, three fp16 MFMAs per product block on
+ *                the 256 x 256 kernels -- error of every score against float64 at or below that of an fp32 GEMM
+ *                relative to the score's own scale sum_k |u_k||i_k| (pieces exact for every element within 2^-18 of its
+ *                row's maximum), whatever the other rows hold, and a row's pieces are the same in a shard, an item range
+ *                and the whole catalogue; half the MFMAs of form 1.  The rows' scale words need no scratch of their own:
+ *                they sit in the third of the pieces' region that two fp16 pieces leave unused (the workspace sizes are
+ *                unchanged).  Taken wherever the call brings the pieces' scratch
  *                (hsk_mf_eval_planes_bytes / hsk_mf_eval_fused_ws_bytes_dim) and dim % 4 == 0 with 16-byte aligned
  *                tables; any other call runs form 1;
  *   1            three bf16 pieces per operand, six bf16 MFMAs per product block (no scaling: the whole fp32 range);
@@ -625,7 +629,9 @@ int hsk_topk_dense(const float* logits, int64_t rows, int64_t cols, int64_t ld, 
                    float* out_vals, int64_t* out_idx, hsk_stream_t stream);
 
 /* merge n_parts candidate lists [n_parts, rows, k] (e.g. all-gathered item shards) into the global
- * top-k per row, same ordering rule. */
+ * top-k per row, same ordering rule.  A list shorter than k is filled up with pads (-inf, id 0x7fffffff): an entry
+ * with that id ranks below every real entry whatever its value, and comes back as such a pad if fewer than k real
+ * entries exist. */
 int hsk_topk_merge(const float* vals, const int32_t* idx, int64_t n_parts, int64_t rows, int64_t k,
                    float* out_vals, int32_t* out_idx, hsk_stream_t stream);
 

@@ -1,11 +1,24 @@
-"""Seeded slices of the two randomised sweeps of the training step, collected by pytest.
+"""Seeded slices of the randomised sweeps (two of the training step, one of evaluation), collected by pytest.
 
 tests/stress_step.py (fused step vs the oracle over random shapes, `big` = the item-partitioned forward's range) and
 tools/stress_pipeline.py (in-launch pipeline vs side-stream prefetch, bit for bit) found real bugs but run only by hand
 and by the clock.  Here: fixed seeds and a fixed number of cases per seed, so two runs execute the same cases.  The
 seeds are chosen so that the library refuses none of these cases up front and every pipeline case really pipelines
 (no sampled softmax, no D = 768: those have no pipeline); a case that comes back refused or un-pipelined fails, so
-nothing is silently left out if the sweeps' draws change."""
+nothing is silently left out if the sweeps' draws change.
+
+tools/stress_eval.py (fused vs materialised top-k, scores against float64 globally and per element, physical shards, row
+scales, the exact integer / tie constructions of tests/eval_cases.py; every arithmetic form) is sliced the same way: 12
+cases for each of three seeds.  The seeds were chosen by replaying the draws on the CPU (stress_eval.draw_case) so that
+EACH of them holds: >= 16 384 items scored in one call (seed 5 case 7: 23 725 items, k = 128; seed 18 cases 0 and 6:
+35 081 items at k = 1, 17 551 in an integer `hidden` case; seed 34 case 9: 42 818 as a physical shard), D = 30 -- rows that
+are not 16-byte aligned: scalar staging, form 1 whatever is set -- (seed 5 cases 9, 11; seed 18 cases 3, 4, 8; seed 34
+case 7), a physical shard (seed 5: seven cases; seed 18 cases 2, 7; seed 34 cases 1, 2, 7, 9), a case without exclusions
+(seed 5 cases 7, 9, 10; seed 18 cases 0, 1; seed 34: six), k = 1 (seed 5 cases 1-3; seed 18 cases 0, 1, 9; seed 34 case
+3), an integer case (seed 5: rising, last_tile twice, saw_down; seed 18: rising twice, hidden, last_tile, saw_up; seed 34:
+equal, quantised); row scales on either table occur in nine cases.  test_stress_eval_slice asserts that these properties
+are still there.  Wall time on an MI355X: a few seconds for the three seeds (1.3 + 0.95 + 0.2 s for the first choice of
+seeds, the same number of cases)."""
 import os
 import sys
 
@@ -21,6 +34,7 @@ pytestmark = pytest.mark.gpu
 STEP_SEEDS, STEP_CASES = (2, 4, 7), 6            # every shape class: D 6 .. 2048, batches 1 .. 4500, all three losses
 BIG_SEEDS, BIG_CASES = (7, 11, 12), 4            # D 256 .. 2048, batches >= 2048, item tables of 5 .. 40 MB
 PIPE_SEEDS, PIPE_CASES, PIPE_DIMS = (7, 9, 12), 4, (256, 512, 1024)
+EVAL_SEEDS, EVAL_CASES = (5, 18, 34), 12
 
 
 @pytest.mark.parametrize('big,seed', [(False, s) for s in STEP_SEEDS] + [(True, s) for s in BIG_SEEDS],
@@ -47,3 +61,18 @@ def test_stress_pipeline_slice(seed):
             assert desc['pipelined_steps'] > 0, f'case {k} of seed {seed} did not pipeline: {desc}'
     finally:
         lib.hsk_bprmf_set_pipeline(1)
+
+
+@pytest.mark.parametrize('seed', EVAL_SEEDS)
+def test_stress_eval_slice(seed):
+    import stress_eval
+    rng = np.random.RandomState(seed)
+    seen = set()
+    for k in range(EVAL_CASES):
+        ok, desc = stress_eval.one_case(rng)
+        assert ok is True, f'case {k} of seed {seed}: {desc}'
+        seen |= {name for name, hit in (('wide', desc['cnt'] >= 16384), ('d30', desc['D'] == 30), ('shard', desc['shard']),
+                                        ('plain', not desc['excl'] and desc['integer'] is None), ('k1', desc['k'] == 1),
+                                        ('integer', desc['integer'] is not None)) if hit}
+    want = {'wide', 'd30', 'shard', 'plain', 'k1', 'integer'}
+    assert want <= seen, f'seed {seed} no longer draws {sorted(want - seen)}: choose the seeds again (stress_eval.draw_case)'
