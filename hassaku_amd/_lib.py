@@ -164,6 +164,12 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p]),
     'hsk_knn_topk_rows': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    'hsk_ease_gram_f64': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    'hsk_ease_inverse_ws_bytes': (c_int64, [c_int64]),
+    'hsk_ease_inverse_f64': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'hsk_ease_weights': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    'hsk_ease_score_rows': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

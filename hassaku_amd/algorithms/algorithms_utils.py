@@ -1,16 +1,19 @@
 """Name -> class registry (algorithms/algorithms_utils.py:12-30).  Filled: the slot on the hot path (mf), its
 bias-only sibling (sgdbias), the anchor / prototype models that share the embedding gather and the
-neighbourhood models (uknn, iknn); the reference's other ten algorithms are out of scope.
+neighbourhood models (uknn, iknn) and the linear model (ease); the reference's other nine algorithms are out of scope
+(SURVEY.md section 2).
 
-The registry has two families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
-always has.  `SparseAlgorithmsEnum` holds the sparse-matrix models (fitted once on the train CSR).  Both families are
-reachable by name through `AlgorithmsEnum` (`AlgorithmsEnum['iknn']`, `AlgorithmsEnum.uknn`), so every caller that
-resolves a slot by name -- run_experiment.py, the experiment helpers -- takes either.  `ALGORITHM_NAMES` lists them all.
-Callers use only a slot's `.name` and `.value`.
+The registry has three families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
+always has.  `SparseAlgorithmsEnum` holds the neighbourhood models and `LinearAlgorithmsEnum` the linear one (both
+fitted once on the train CSR).  Every family is reachable by name through `AlgorithmsEnum` (`AlgorithmsEnum['iknn']`,
+`AlgorithmsEnum.ease`), so every caller that resolves a slot by name -- run_experiment.py, the experiment helpers --
+takes any of them.  `ALGORITHM_NAMES` lists the first two families, `ALL_ALGORITHM_NAMES` all three.  Callers use only a
+slot's `.name` and `.value`.
 """
 from enum import Enum, EnumMeta
 
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN
+from hassaku_amd.algorithms.linear_algs import EASE
 from hassaku_amd.algorithms.proto_alg import ACF, IProtoMF, UIProtoMF, UProtoMF
 from hassaku_amd.algorithms.sgd_alg import SGDBaseline, SGDMatrixFactorization
 
@@ -20,19 +23,29 @@ class SparseAlgorithmsEnum(Enum):
     iknn = ItemKNN
 
 
+class LinearAlgorithmsEnum(Enum):
+    ease = EASE
+
+
+_OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum)
+
+
 class _RegistryMeta(EnumMeta):
-    """Looks a name up among the SGD slots first, then among the sparse-matrix slots."""
+    """Looks a name up among the SGD slots first, then among the sparse-matrix and the linear slots."""
 
     def __getitem__(cls, name):
         if name in cls._member_map_:
             return cls._member_map_[name]
-        if name in SparseAlgorithmsEnum.__members__:
-            return SparseAlgorithmsEnum[name]
+        for family in _OTHER_FAMILIES:
+            if name in family.__members__:
+                return family[name]
         raise KeyError(name)
 
     def __getattr__(cls, name):
-        if not name.startswith('_') and name in SparseAlgorithmsEnum.__members__:
-            return SparseAlgorithmsEnum[name]
+        if not name.startswith('_'):
+            for family in _OTHER_FAMILIES:
+                if name in family.__members__:
+                    return family[name]
         if hasattr(EnumMeta, '__getattr__'):   # Python < 3.12 resolves members here
             return super().__getattr__(name)
         raise AttributeError(name)
@@ -48,3 +61,4 @@ class AlgorithmsEnum(Enum, metaclass=_RegistryMeta):
 
 
 ALGORITHM_NAMES = tuple(m.name for m in AlgorithmsEnum) + tuple(m.name for m in SparseAlgorithmsEnum)
+ALL_ALGORITHM_NAMES = ALGORITHM_NAMES + tuple(m.name for m in LinearAlgorithmsEnum)

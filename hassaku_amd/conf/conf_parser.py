@@ -49,12 +49,15 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
     """alg / dataset are members of AlgorithmsEnum / DatasetsEnum (only .name and alg.value are used)."""
     from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
+    from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
     from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 
     assert 'data_path' in conf, 'Data path is missing from the configuration file'
     if issubclass(alg.value, KNNAlgorithm):
         # the neighbourhood models get no SGD defaults (conf/conf_parser.py:121); their own keys are checked here
         validate_knn_conf(conf)
+    elif issubclass(alg.value, EASE):
+        validate_ease_conf(conf)
     conf['alg'] = alg.name
     conf['time_run'] = generate_id()
     conf['dataset'] = dataset.name

@@ -857,3 +857,91 @@ def knn_topk_rows(scores: torch.Tensor, k: int, n_cols: Optional[int] = None):
     ids = torch.empty((R, k), dtype=torch.int32, device=scores.device)
     _lib.check(lib.hsk_knn_topk_rows(_p(scores), R, n_cols, ld, k, _p(vals), _p(ids), _stream()), 'hsk_knn_topk_rows')
     return vals, ids
+
+
+# ---------------------------------------------------------------------------------------------------
+# EASE (hsk_ease.hip)
+# ---------------------------------------------------------------------------------------------------
+STATUS_NOT_SPD = 8
+
+
+def ease_gram_f64(C: torch.Tensor, rows: int, r0: int, lam: int, G: torch.Tensor) -> torch.Tensor:
+    """Rows [r0, r0 + rows) of the fp64 G = counts + lam I from an int32 count block of knn_gram_i8."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(C, torch.int32, 'C')
+    _chk(G, torch.float64, 'G')
+    n = G.shape[0]
+    if G.dim() != 2 or G.shape[1] < n or C.dim() != 2 or C.shape[0] < rows or C.shape[1] < n or r0 + rows > n:
+        raise ValueError(f'G {tuple(G.shape)} / C {tuple(C.shape)} do not hold rows [{r0}, {r0 + rows}) of an n x n Gram')
+    _lib.check(lib.hsk_ease_gram_f64(_p(C), rows, n, C.shape[1], r0, int(lam), _p(G), G.shape[1], _stream()),
+               'hsk_ease_gram_f64')
+    return G
+
+
+def ease_inverse_ws_bytes(n: int) -> int:
+    return int(_lib.load().hsk_ease_inverse_ws_bytes(int(n)))
+
+
+def ease_inverse_f64(A: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In-place inverse of the SPD fp64 matrix A [n, ld >= n] (its first n columns).  Raises (after a synchronising
+    read of the status word) if a pivot was not positive and finite."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(A, torch.float64, 'A')
+    if A.dim() != 2 or A.shape[1] < A.shape[0]:
+        raise ValueError(f'A has shape {tuple(A.shape)}, expected [n, ld >= n]')
+    n, ld = A.shape
+    own = status is None
+    if own:
+        status = torch.zeros(1, dtype=torch.int32, device=A.device)
+    ws = torch.empty(ease_inverse_ws_bytes(n) // 8, dtype=torch.float64, device=A.device)
+    _lib.check(lib.hsk_ease_inverse_f64(_p(A), n, ld, _p(ws), ws.numel() * 8, _p(status), _stream()),
+               'hsk_ease_inverse_f64')
+    if own and int(status.item()) & STATUS_NOT_SPD:
+        raise ArithmeticError('ease_inverse_f64: the matrix is not positive definite in fp64 (bad pivot)')
+    return A
+
+
+def ease_weights(P: torch.Tensor) -> torch.Tensor:
+    """In place B = P / (-diag P) with a zero diagonal."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(P, torch.float64, 'P')
+    if P.dim() != 2 or P.shape[1] < P.shape[0]:
+        raise ValueError(f'P has shape {tuple(P.shape)}, expected [n, ld >= n]')
+    nd = torch.empty(P.shape[0], dtype=torch.float64, device=P.device)
+    _lib.check(lib.hsk_ease_weights(_p(P), P.shape[0], P.shape[1], _p(nd), _stream()), 'hsk_ease_weights')
+    return P
+
+
+def ease_score_rows(users: torch.Tensor, x_csr, B: torch.Tensor, window: int = 1024, excl=None,
+                    out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [R, n_items]: row q = sum of the rows of B picked by the items of train row users[q], in stored order.
+    x_csr: (indptr int64, indices int32, n_users); excl: (indptr, indices) -> those columns -inf."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(users, torch.int64, 'users')
+    R = users.numel()
+    xp, xi, n_users = x_csr
+    _chk(xp, torch.int64, 'x_indptr', (n_users + 1,))
+    _chk(xi, torch.int32, 'x_indices')
+    _chk(B, torch.float64, 'B')
+    if B.dim() != 2 or B.shape[1] < B.shape[0]:
+        raise ValueError(f'B has shape {tuple(B.shape)}, expected [n_items, ld >= n_items]')
+    n_items = B.shape[0]
+    ep, ei = excl if excl is not None else (None, None)
+    if excl is not None:
+        _chk(ep, torch.int64, 'excl_indptr')
+        _chk(ei, torch.int32, 'excl_indices')
+    if out is None:
+        out = torch.empty((R, n_items), dtype=torch.float64, device=users.device)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_items:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_items})')
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    _lib.check(lib.hsk_ease_score_rows(_p(users), R, n_users, _p(xp), _p(xi), _p(B), n_items, B.shape[1],
+                                       max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1], _p(status),
+                                       _stream()), 'hsk_ease_score_rows')
+    return out

@@ -704,6 +704,42 @@ int hsk_knn_score_rows(const int64_t* users, int64_t n_users, int64_t n_a_rows, 
 int hsk_knn_topk_rows(const double* scores, int64_t rows, int64_t n_cols, int64_t ld, int64_t k, double* out_vals,
                       int32_t* out_idx, hsk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * EASE (algorithms/linear_algs.py:131-176): G = X^T X + int(lam) I, P = G^-1, B = P / (-diag P) with a zero
+ * diagonal, pred = X B
+ * ------------------------------------------------------------------------------------------ */
+
+enum { HSK_STATUS_NOT_SPD = 8 }; /* hsk_ease_inverse_f64 met a pivot that is not positive and finite */
+
+/* fp64 Gram rows from a count block of hsk_knn_gram_i8 on the packed X^T: G[r0 + i, j] = (double) C[i, j], plus lam
+ * where r0 + i == j, for i < rows, j < n (C leading dimension ldc, G n x n with leading dimension ld).  The counts
+ * are exact, so for a binary X this is linear_algs.py:151-154 bitwise. */
+int hsk_ease_gram_f64(const int32_t* C, int64_t rows, int64_t n, int64_t ldc, int64_t r0, int64_t lam, double* G,
+                      int64_t ld, hsk_stream_t stream);
+
+/* bytes of the workspace of hsk_ease_inverse_f64: two 64 x n_pad fp64 panels and one 64 x 64 block */
+int64_t hsk_ease_inverse_ws_bytes(int64_t n);
+
+/* in-place inverse of the symmetric positive definite fp64 n x n matrix A (leading dimension ld): blocked
+ * Gauss-Jordan without pivoting, block width 64, the rank-64 update on v_mfma_f64_16x16x4_f64 (replaces
+ * numpy.linalg.inv, linear_algs.py:156).  workspace: device memory, 16-byte aligned, workspace_bytes >=
+ * hsk_ease_inverse_ws_bytes(n).  A pivot that is not positive and finite sets HSK_STATUS_NOT_SPD in *status. */
+int hsk_ease_inverse_f64(double* A, int64_t n, int64_t ld, void* workspace, int64_t workspace_bytes, int32_t* status,
+                         hsk_stream_t stream);
+
+/* in place P[i, j] <- P[i, j] / (-P[j, j]) for i != j, 0 on the diagonal: one IEEE division per element, as numpy's
+ * `P / (-np.diag(P))` (linear_algs.py:158-159).  neg_diag: n doubles of device scratch. */
+int hsk_ease_weights(double* P, int64_t n, int64_t ld, double* neg_diag, hsk_stream_t stream);
+
+/* fp64 score rows (linear_algs.py:161 `matrix @ B`): out[q, j] = ((0 + B[i1, j]) + B[i2, j]) + ... over the items
+ * of train row users[q] in stored order (scipy's csr @ dense order); B n_items x n_items with leading dimension ldb.
+ * One workgroup per (user, window of `window` columns).  excl_indptr / excl_indices and *status as in
+ * hsk_knn_score_rows. */
+int hsk_ease_score_rows(const int64_t* users, int64_t n_rows, int64_t n_users, const int64_t* x_indptr,
+                        const int32_t* x_indices, const double* B, int64_t n_items, int64_t ldb, int64_t window,
+                        const int64_t* excl_indptr, const int32_t* excl_indices, double* out, int64_t ld,
+                        int32_t* status, hsk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
