@@ -86,6 +86,12 @@ __device__ __forceinline__ int hsk_readlane_i(int v, int lane) {
   return __builtin_amdgcn_readlane(v, lane);
 }
 __device__ __forceinline__ int hsk_uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// v_writelane_b32: `old` with lane `lane` (wave-uniform) replaced by the wave-uniform `v`.  clang has no builtin for it;
+// the intrinsic is declared by name, so the compiler still schedules it and inserts the wait states it needs.
+extern "C" __device__ int hsk_llvm_writelane_i32(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+__device__ __forceinline__ float hsk_writelane_f(float v, int lane, float old) {
+  return __int_as_float(hsk_llvm_writelane_i32(__float_as_int(v), lane, __float_as_int(old)));
+}
 
 // ---- small fixed-width float vectors (1, 2 or 4 floats = one global_load_dword/x2/x4) ----------
 template <int V> struct hsk_vec;

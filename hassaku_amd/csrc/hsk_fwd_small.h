@@ -73,24 +73,7 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_ugrad_wg(const float* __restric
   while (nr > 0) {
     float gv = 0.f, xv = 0.f;
     auto process = [&](Row(&buf)[R], int j) {
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (j + r < nr) {
-          const float s = hsk_wave_sum(hsk_row_dot_partial(ur, buf[r])) + hsk_readlane_f(mybias, j + r);
-          float g;
-          if (LOSS == HSK_LOSS_BPR) {
-            const float x = s0 - s;
-            g = inv_norm / (1.f + expf(x));     // sigma(-x)/(B*N)
-            gsum += g;
-            xv = (lane == j + r) ? x : xv;
-          } else {
-            g = inv_norm / (1.f + expf(-s));    // sigma(s)/(B*K), label 0
-            xv = (lane == j + r) ? s : xv;
-          }
-          hsk_row_axpy(acc, g, buf[r]);
-          gv = (lane == j + r) ? g : gv;
-        }
-      }
+      hsk_weigh_rows<LOSS>(ur, buf, j, nr, lane, mybias, s0, inv_norm, acc, gsum, gv, xv);
     };
     for (int j = 0; j < nr; j += 2 * R) {
       prefetch(bufB, j + R);

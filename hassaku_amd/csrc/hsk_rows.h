@@ -110,6 +110,45 @@ __device__ __forceinline__ float hsk_softplus(float z) {
   return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
 }
 
+// Weigh the rows of one buffer (BPR and BCE): buf[0..R) hold entries j .. j+R-1 of a chunk of nr <= 64 entries, lane l
+// of `mybias` holds entry l's item bias.  The score of entry j+r is written into lane j+r of one vector, so x and
+// g = d loss / d s are evaluated ONCE per buffer, lane-parallel, instead of once per row in all 64 lanes (expf, the
+// IEEE division and the lane selects were 32 of the 56 vector instructions a row cost).  expf and '/' are pure per-lane
+// functions and the reduction tree, the operands of the bias add, the order of gsum and of the axpys are what the
+// row-by-row loop had: identical bits.  Lanes outside [j, j+R) n [0, nr) carry garbage through expf and the division;
+// they reach neither gv / xv (the chunk's per-lane g and x, merged here) nor gsum nor acc.
+template <int LOSS, int V, int NCH, int R>
+__device__ __forceinline__ void hsk_weigh_rows(const hsk_row<V, NCH>& ur, const hsk_row<V, NCH> (&buf)[R], int j, int nr,
+                                               int lane, float mybias, float s0, float inv_norm, hsk_row<V, NCH>& acc,
+                                               float& gsum, float& gv, float& xv) {
+  static_assert(LOSS == HSK_LOSS_BPR || LOSS == HSK_LOSS_BCE, "the sampled softmax keeps a running max: row by row");
+  if (j >= nr) return;
+  float sv = 0.f;
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (j + r < nr) sv = hsk_writelane_f(hsk_wave_sum(hsk_row_dot_partial(ur, buf[r])), j + r, sv);
+  const float s = sv + mybias;
+  float x, g;
+  if (LOSS == HSK_LOSS_BPR) {
+    x = s0 - s;
+    g = inv_norm / (1.f + expf(x));    // sigma(-x)/(B*N) = d loss / d s_neg
+  } else {
+    x = s;
+    g = inv_norm / (1.f + expf(-s));   // sigma(s)/(B*K), label 0
+  }
+  const bool mine = lane >= j && lane < min(j + R, nr);
+  gv = mine ? g : gv;
+  xv = mine ? x : xv;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (j + r < nr) {
+      const float gr = hsk_readlane_f(g, j + r);
+      if (LOSS == HSK_LOSS_BPR) gsum += gr;   // row order
+      hsk_row_axpy(acc, gr, buf[r]);
+    }
+  }
+}
+
 __device__ __forceinline__ int hsk_clamp_index(long long idx, long long n, int32_t* status) {
   if (idx < 0 || idx >= n) {
     if (status) atomicOr(status, HSK_STATUS_BAD_INDEX);

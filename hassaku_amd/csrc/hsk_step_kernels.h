@@ -203,23 +203,13 @@ __global__ __launch_bounds__(256) void k_fwd_ugrad(const float* __restrict__ Uw,
     }
 
     auto process = [&](Row(&buf)[R], int j) {
+      if constexpr (LOSS != HSK_LOSS_SSM) {   // BPR, BCE: the buffer's rows are weighed in one pass
+        hsk_weigh_rows<LOSS>(ur, buf, j, nr, lane, mybias, s0, inv_norm, acc, gsum, gv, xv);
+      } else {
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
-        if (j + r < nr) {
-          const float s = hsk_wave_sum(hsk_row_dot_partial(ur, buf[r])) + hsk_readlane_f(mybias, j + r);
-          if (LOSS == HSK_LOSS_BPR) {
-            const float x = s0 - s;
-            const float g = inv_norm / (1.f + expf(x));  // sigma(-x)/(B*N) = d loss / d s_neg
-            hsk_row_axpy(acc, g, buf[r]);
-            gsum += g;
-            gv = (lane == j + r) ? g : gv;
-            xv = (lane == j + r) ? x : xv;
-          } else if (LOSS == HSK_LOSS_BCE) {
-            const float g = inv_norm / (1.f + expf(-s));  // sigma(s)/(B*K), label 0
-            hsk_row_axpy(acc, g, buf[r]);
-            gv = (lane == j + r) ? g : gv;
-            xv = (lane == j + r) ? s : xv;
-          } else {
+        for (int r = 0; r < R; ++r) {
+          if (j + r < nr) {
+            const float s = hsk_wave_sum(hsk_row_dot_partial(ur, buf[r])) + hsk_readlane_f(mybias, j + r);
             const float z = s + ssm_c;
             if (z > smax) {  // wave-uniform branch: rescale what has been accumulated so far
               const float f = expf(smax - z);
