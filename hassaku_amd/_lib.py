@@ -170,6 +170,11 @@ SIGNATURES = {
     'hsk_ease_weights': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     'hsk_ease_score_rows': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    'hsk_p3_inv_degrees': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    'hsk_p3_gram_f64': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                c_int64, c_void_p]),
+    'hsk_p3_score_rows': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                  c_double, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

@@ -1,17 +1,19 @@
 """Name -> class registry (algorithms/algorithms_utils.py:12-30).  Filled: the slot on the hot path (mf), its
 bias-only sibling (sgdbias), the anchor / prototype models that share the embedding gather and the
-neighbourhood models (uknn, iknn) and the linear model (ease); the reference's other nine algorithms are out of scope
-(SURVEY.md section 2).
+neighbourhood models (uknn, iknn), the linear model (ease) and the graph model (p3alpha); the reference's other
+algorithms are out of scope.
 
-The registry has three families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
-always has.  `SparseAlgorithmsEnum` holds the neighbourhood models and `LinearAlgorithmsEnum` the linear one (both
-fitted once on the train CSR).  Every family is reachable by name through `AlgorithmsEnum` (`AlgorithmsEnum['iknn']`,
-`AlgorithmsEnum.ease`), so every caller that resolves a slot by name -- run_experiment.py, the experiment helpers --
-takes any of them.  `ALGORITHM_NAMES` lists the first two families, `ALL_ALGORITHM_NAMES` all three.  Callers use only a
-slot's `.name` and `.value`.
+The registry has four families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
+always has.  `SparseAlgorithmsEnum` holds the neighbourhood models, `LinearAlgorithmsEnum` the linear one and
+`GraphAlgorithmsEnum` the random-walk one (all fitted once on the train CSR).  Every family is reachable by name
+through `AlgorithmsEnum` (`AlgorithmsEnum['iknn']`, `AlgorithmsEnum.ease`, `AlgorithmsEnum.p3alpha`), so every caller
+that resolves a slot by name -- run_experiment.py, the experiment helpers -- takes any of them.  `ALGORITHM_NAMES` lists the first two families, `ALL_ALGORITHM_NAMES` the first three and
+`REGISTERED_ALGORITHM_NAMES` all four (the earlier tuples keep their contents).  Callers use only a slot's `.name` and
+`.value`.
 """
 from enum import Enum, EnumMeta
 
+from hassaku_amd.algorithms.graph_algs import P3alpha
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN
 from hassaku_amd.algorithms.linear_algs import EASE
 from hassaku_amd.algorithms.proto_alg import ACF, IProtoMF, UIProtoMF, UProtoMF
@@ -27,11 +29,15 @@ class LinearAlgorithmsEnum(Enum):
     ease = EASE
 
 
-_OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum)
+class GraphAlgorithmsEnum(Enum):
+    p3alpha = P3alpha
+
+
+_OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum, GraphAlgorithmsEnum)
 
 
 class _RegistryMeta(EnumMeta):
-    """Looks a name up among the SGD slots first, then among the sparse-matrix and the linear slots."""
+    """Looks a name up among the SGD slots first, then among the sparse-matrix, the linear and the graph slots."""
 
     def __getitem__(cls, name):
         if name in cls._member_map_:
@@ -62,3 +68,4 @@ class AlgorithmsEnum(Enum, metaclass=_RegistryMeta):
 
 ALGORITHM_NAMES = tuple(m.name for m in AlgorithmsEnum) + tuple(m.name for m in SparseAlgorithmsEnum)
 ALL_ALGORITHM_NAMES = ALGORITHM_NAMES + tuple(m.name for m in LinearAlgorithmsEnum)
+REGISTERED_ALGORITHM_NAMES = ALL_ALGORITHM_NAMES + tuple(m.name for m in GraphAlgorithmsEnum)

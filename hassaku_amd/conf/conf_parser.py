@@ -48,6 +48,7 @@ def _fill(target: dict, defaults, added: list):
 def parse_conf(conf: dict, alg, dataset) -> dict:
     """alg / dataset are members of AlgorithmsEnum / DatasetsEnum (only .name and alg.value are used)."""
     from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm
+    from hassaku_amd.algorithms.graph_algs import P3alpha, validate_p3alpha_conf
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
     from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
     from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
@@ -58,6 +59,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
         validate_knn_conf(conf)
     elif issubclass(alg.value, EASE):
         validate_ease_conf(conf)
+    elif issubclass(alg.value, P3alpha):
+        validate_p3alpha_conf(conf)
     conf['alg'] = alg.name
     conf['time_run'] = generate_id()
     conf['dataset'] = dataset.name

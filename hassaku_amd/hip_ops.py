@@ -945,3 +945,74 @@ def ease_score_rows(users: torch.Tensor, x_csr, B: torch.Tensor, window: int = 1
                                        max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1], _p(status),
                                        _stream()), 'hsk_ease_score_rows')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# P3alpha (hsk_p3.hip)
+# ---------------------------------------------------------------------------------------------------
+def p3_inv_degrees(indptr: torch.Tensor, n_out: Optional[int] = None) -> torch.Tensor:
+    """fp64 [n_out >= n]: 1 / degree of each row of a CSR (indptr int64 [n + 1]), 0.0 for degree 0 and for padding."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    n = indptr.numel() - 1
+    _chk(indptr, torch.int64, 'indptr', (n + 1,))
+    n_out = n if n_out is None else int(n_out)
+    out = torch.empty(n_out, dtype=torch.float64, device=indptr.device)
+    _lib.check(lib.hsk_p3_inv_degrees(_p(indptr), n, _p(out), n_out, _stream()), 'hsk_p3_inv_degrees')
+    return out
+
+
+def p3_gram_f64(M: torch.Tensor, n: int, col_weight: torch.Tensor, r0: int, r1: int, out: torch.Tensor,
+                row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows [r0, r1) of out[i, j] = row_scale[i] * sum_u M[i, u] col_weight[u] M[j, u] (fp64 matrix cores) from the
+    int8 image M [rows_pad, k_pad] of knn_pack_i8; col_weight fp64 [k_pad]; out fp64 [n, ld >= n]; r0 a multiple of
+    128."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(M, torch.int8, 'M')
+    rp, kp = M.shape
+    _chk(col_weight, torch.float64, 'col_weight', (kp,))
+    _chk(row_scale, torch.float64, 'row_scale', (n,), optional=True)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] < n or out.shape[1] < n:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({n}, {n})')
+    _lib.check(lib.hsk_p3_gram_f64(_p(M), n, rp, kp, _p(col_weight), _p(row_scale), r0, r1, _p(out), out.shape[1],
+                                   _stream()), 'hsk_p3_gram_f64')
+    return out
+
+
+def p3_score_rows(users: torch.Tensor, x_csr, W: torch.Tensor, inv_deg_u: torch.Tensor, alpha: float,
+                  window: int = 1024, excl=None, out: Optional[torch.Tensor] = None,
+                  status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [R, n_items]: row q = (inv_deg_u[u] * sum of the rows of W picked by the items of train row u = users[q],
+    in stored order) ** alpha.  x_csr: (indptr int64, indices int32, n_users); excl: (indptr, indices) -> those
+    columns -inf."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(users, torch.int64, 'users')
+    R = users.numel()
+    xp, xi, n_users = x_csr
+    _chk(xp, torch.int64, 'x_indptr', (n_users + 1,))
+    _chk(xi, torch.int32, 'x_indices')
+    _chk(W, torch.float64, 'W')
+    if W.dim() != 2 or W.shape[1] < W.shape[0]:
+        raise ValueError(f'W has shape {tuple(W.shape)}, expected [n_items, ld >= n_items]')
+    n_items = W.shape[0]
+    if inv_deg_u.numel() < n_users:
+        raise ValueError(f'inv_deg_u has {inv_deg_u.numel()} entries, needs {n_users}')
+    _chk(inv_deg_u, torch.float64, 'inv_deg_u')
+    ep, ei = excl if excl is not None else (None, None)
+    if excl is not None:
+        _chk(ep, torch.int64, 'excl_indptr')
+        _chk(ei, torch.int32, 'excl_indices')
+    if out is None:
+        out = torch.empty((R, n_items), dtype=torch.float64, device=users.device)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_items:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_items})')
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    _lib.check(lib.hsk_p3_score_rows(_p(users), R, n_users, _p(xp), _p(xi), _p(W), n_items, W.shape[1], _p(inv_deg_u),
+                                     float(alpha), max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1],
+                                     _p(status), _stream()), 'hsk_p3_score_rows')
+    return out

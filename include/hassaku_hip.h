@@ -740,6 +740,33 @@ int hsk_ease_score_rows(const int64_t* users, int64_t n_rows, int64_t n_users, c
                         const int64_t* excl_indptr, const int32_t* excl_indices, double* out, int64_t ld,
                         int32_t* status, hsk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * P3alpha (algorithms/graph_algs.py:9-88): with w = 1 / degree (0 for degree 0),
+ * S = X^T diag(w_u) X, W = diag(w_i) S, pred[u, j] = (w_u sum_{i in items(u)} W[i, j]) ^ alpha
+ * ------------------------------------------------------------------------------------------ */
+
+/* out[i] = 1 / (indptr[i + 1] - indptr[i]) for i < n, 0.0 where that degree is 0 and for i in [n, n_out): the
+ * reciprocal degrees of a CSR's rows, padded to the k_pad of the int8 operand (one IEEE division each). */
+int hsk_p3_inv_degrees(const int64_t* indptr, int64_t n, double* out, int64_t n_out, hsk_stream_t stream);
+
+/* rows [r0, r1) of the weighted fp64 Gram out[i, j] = row_scale[i] * sum_u M[i, u] col_weight[u] M[j, u], j < n, on
+ * v_mfma_f64_16x16x4_f64.  M: the int8 image [rows_pad, k_pad] of hsk_knn_pack_i8 (of X^T); col_weight fp64 [k_pad]
+ * (zero for padding); row_scale fp64 [n] or NULL for 1; out n x n with leading dimension ld >= n, rows >= n and
+ * columns in [n, ld) never written; r0 a multiple of 128.  M and col_weight 16-byte aligned.  Every product is 0 or
+ * col_weight[u] exactly and rows and columns add in the same k order: with row_scale NULL the result is bitwise
+ * symmetric, and an entry with a single common u is that col_weight[u]. */
+int hsk_p3_gram_f64(const int8_t* M, int64_t n, int64_t rows_pad, int64_t k_pad, const double* col_weight,
+                    const double* row_scale, int64_t r0, int64_t r1, double* out, int64_t ld, hsk_stream_t stream);
+
+/* fp64 score rows: out[q, j] = pow(inv_deg_u[u] * (((0 + W[i1, j]) + W[i2, j]) + ...), alpha) over the items of train
+ * row u = users[q] in stored order; W n_items x n_items with leading dimension ldw; inv_deg_u fp64 [n_users].  With
+ * alpha == 1.0 no pow is evaluated (the row is bitwise the product); a zero sum gives +0.0.  alpha in (0, inf).
+ * Windows, excl_indptr / excl_indices and *status as in hsk_ease_score_rows. */
+int hsk_p3_score_rows(const int64_t* users, int64_t n_rows, int64_t n_users, const int64_t* x_indptr,
+                      const int32_t* x_indices, const double* W, int64_t n_items, int64_t ldw, const double* inv_deg_u,
+                      double alpha, int64_t window, const int64_t* excl_indptr, const int32_t* excl_indices, double* out,
+                      int64_t ld, int32_t* status, hsk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
