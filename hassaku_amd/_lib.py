@@ -175,6 +175,17 @@ SIGNATURES = {
                                 c_int64, c_void_p]),
     'hsk_p3_score_rows': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                   c_double, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    'hsk_svd_spmm_f64': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                 c_void_p]),
+    'hsk_svd_gram_ws_bytes': (c_int64, [c_int64, c_int64]),
+    'hsk_svd_gram_f64': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                 c_int64, c_void_p]),
+    'hsk_svd_mul_f64': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                c_void_p]),
+    'hsk_svd_residuals_f64': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+                                      c_void_p]),
+    'hsk_svd_score_rows': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

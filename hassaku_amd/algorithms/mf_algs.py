@@ -1,0 +1,220 @@
+"""SVD on the HIP device (algorithms/mf_algs.py:13-65 of the reference, which calls scipy.sparse.linalg.svds).
+
+The leading k = n_factors singular triplets of the binary user x item train matrix X by block subspace iteration with
+Rayleigh-Ritz on A = X^T X, which is never formed.  With b = min(round_up(k + OVERSAMPLE, 16),
+n_users, n_items) columns:
+    V  <- orth(orth(V0))                      V0 = RandomState(SEED).standard_normal((n_items, b)), made on the host
+    repeat (at most MAX_ITER times):
+        Z = X V,  Y = X^T Z                   hsk_svd_spmm_f64 on the CSR of X and of X^T
+        H = Z^T Z (= V^T A V)                 hsk_svd_gram_f64; symmetrised, eigh on the host, theta descending
+        V' = V Q,  Y' = Y Q                   hsk_svd_mul_f64
+        r_j = || Y'[:, j] - theta_j V'[:, j] ||      hsk_svd_residuals_f64
+        stop when max_{j < k} r_j <= TOL theta_1
+        V  <- orth(orth(Y'))
+    items_factors = V'[:, :k],  users_factors = X items_factors (= U S),  singular_values = sqrt(theta[:k])
+orth(Y) normalises the columns (zero columns are dropped), takes the Gram M = Y^T Y on the device and eigh(M) on the
+host, drops the directions with w <= width 2^-52 w_max and returns Y (Q_kept / sqrt(w_kept)): no Cholesky, no pivot to
+fail, and a block that shrinks when X has fewer independent directions than b.  The host's share is b x b.
+The reference's dense users x items product is never built: score_rows() multiplies the factor rows on the fp64
+matrix cores.  svds' ascending column order and its signs are not reproduced; the product of the factors is what the
+two share."""
+import logging
+import os
+
+import numpy as np
+import torch
+
+from hassaku_amd import hip_ops
+from hassaku_amd.algorithms.base_classes import SparseMatrixBasedRecommenderAlgorithm
+from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, _csr_arrays, _transpose
+
+
+def _n_factors(n_factors) -> int:
+    """n_factors as an int, refusing bools, non-integers and values below 1."""
+    if isinstance(n_factors, (bool, np.bool_)) or not isinstance(n_factors, (int, np.integer)):
+        raise ValueError(f'n_factors = {n_factors!r} must be an integer')
+    if n_factors < 1:
+        raise ValueError(f'n_factors = {n_factors!r} must be >= 1')
+    return int(n_factors)
+
+
+def validate_svd_conf(conf: dict):
+    """The SVD key of a conf (mf_algs.py:65): `n_factors`, required as the reference's build_from_conf does."""
+    if 'n_factors' not in conf:
+        raise ValueError('SVDAlgorithm conf needs n_factors')
+    _n_factors(conf['n_factors'])
+
+
+class SVDAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
+    OVERSAMPLE = 32              # columns of the block beyond n_factors (before rounding up to 16)
+    TOL = 1e-11                  # residual of the n_factors leading Ritz pairs, relative to theta_1
+    MAX_ITER = 1000
+    SEED = 0                     # of the host-made start block
+
+    def __init__(self, n_factors=100, device='cuda'):
+        super().__init__()
+        self.n_factors = _n_factors(n_factors)
+        self.device = torch.device(device)
+        self.name = 'SVDAlgorithm'
+        self.pred_mtx = None          # never set: _dense_rows is not used, the factors are all a file holds
+        self.users_factors = None     # fp64 [n_users, k] on the device (= U S); a view of an even-stride buffer
+        self.items_factors = None     # fp64 [n_items, k]
+        self.singular_values = None   # numpy float64 [k], descending (None for a model loaded from the reference)
+        self.n_users = self.n_items = None
+        self.n_iter_ = self.residual_ = None
+        self._status = None
+        logging.info('Built %s: n_factors %d', self.name, self.n_factors)
+
+    # ------------------------------------------------------------------ fit
+    def block_width(self, n_users: int, n_items: int) -> int:
+        return min(-(-(self.n_factors + self.OVERSAMPLE) // 16) * 16, n_users, n_items)
+
+    def fit_bytes(self, n_users: int, n_items: int) -> int:
+        """Device bytes fit() allocates: Z [n_users, b], three [n_items, b] blocks and the Gram workspace."""
+        b = hip_ops.svd_ld(self.block_width(n_users, n_items))
+        return (n_users + 3 * n_items) * b * 8 + self._gram_ws_bytes(n_users, n_items, b)
+
+    @staticmethod
+    def _gram_ws_bytes(n_users: int, n_items: int, b: int) -> int:
+        """The Gram workspace that serves Z and the item blocks at every width the block may shrink to (a narrower
+        block has fewer tiles and so more row splits: its workspace is not always the smaller one)."""
+        return max(hip_ops.svd_gram_ws_bytes(n, w) for n in (n_users, n_items) for w in range(1, b + 1))
+
+    def _forget(self):
+        self.users_factors = self.items_factors = self.singular_values = None
+        self.n_iter_ = self.residual_ = None
+
+    def _orth(self, Y, scratch, out, ws):
+        """orth(Y) into the leading columns of `out`, the normalised block in `scratch` (both [n, >= width])."""
+        dev, width = Y.device, Y.shape[1]
+        norms = hip_ops.svd_residuals(Y, Y, torch.zeros(width, dtype=torch.float64, device=dev)).cpu().numpy()
+        keep = np.flatnonzero(norms > 0)
+        D = np.zeros((width, hip_ops.svd_ld(len(keep))))
+        D[keep, np.arange(len(keep))] = 1.0 / norms[keep]
+        Yn = hip_ops.svd_mul(Y, torch.from_numpy(D).to(dev)[:, :len(keep)], out=scratch[:, :len(keep)])
+        M = hip_ops.svd_gram(Yn, ws=ws).cpu().numpy()
+        w, Q = np.linalg.eigh((M + M.T) / 2)
+        good = w > len(keep) * 2.0 ** -52 * w.max()
+        R = np.zeros((len(keep), hip_ops.svd_ld(int(good.sum()))))
+        R[:, :int(good.sum())] = Q[:, good] / np.sqrt(w[good])
+        return hip_ops.svd_mul(Yn, torch.from_numpy(R).to(dev)[:, :int(good.sum())], out=out[:, :int(good.sum())])
+
+    def fit(self, matrix):
+        indptr, indices, n_users, n_items = _csr_arrays(matrix)
+        k, dev = self.n_factors, self.device
+        if not 1 <= k < min(n_users, n_items):     # what svds demands of k
+            raise ValueError(f'n_factors = {k} must be in [1, min(n_users, n_items) = {min(n_users, n_items)})')
+        b = self.block_width(n_users, n_items)
+        if b > hip_ops.SVD_MAX_BLOCK:
+            raise ValueError(f'n_factors = {k} gives a block of {b} columns, at most {hip_ops.SVD_MAX_BLOCK}')
+        need = self.fit_bytes(n_users, n_items)
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > free:
+            raise ValueError(f'{self.name}.fit on {n_users} users x {n_items} items needs {need} bytes of device '
+                             f'memory, {free} are free')
+        self._forget()                     # a fit that raises leaves no model behind
+        x_ptr, x_idx = torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev)
+        t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n_items)
+        X, Xt = (x_ptr, x_idx, n_items), (t_ptr, t_idx, n_users)
+        ld = hip_ops.svd_ld(b)
+        Zbuf = torch.empty((n_users, ld), dtype=torch.float64, device=dev)
+        P, S, T = (torch.empty((n_items, ld), dtype=torch.float64, device=dev) for _ in range(3))
+        ws = torch.empty(self._gram_ws_bytes(n_users, n_items, ld) // 8, dtype=torch.float64, device=dev)
+        V0 = np.zeros((n_items, ld))
+        V0[:, :b] = np.random.RandomState(self.SEED).standard_normal((n_items, b))
+        S.copy_(torch.from_numpy(V0))
+        V = self._orth(self._orth(S[:, :b], T, P, ws), T, S, ws)      # V lives in S; P and T are free
+        for it in range(1, self.MAX_ITER + 1):
+            bc = V.shape[1]
+            if bc < k:
+                raise ValueError(f'the train matrix has rank {bc} < n_factors = {k}')
+            Z = hip_ops.svd_spmm(X, V, out=Zbuf[:, :bc])
+            Y = hip_ops.svd_spmm(Xt, Z, out=P[:, :bc])
+            H = hip_ops.svd_gram(Z, ws=ws).cpu().numpy()
+            theta, Q = np.linalg.eigh((H + H.T) / 2)
+            theta = np.ascontiguousarray(theta[::-1])
+            Qd = torch.zeros((bc, hip_ops.svd_ld(bc)), dtype=torch.float64)
+            Qd[:, :bc] = torch.from_numpy(np.ascontiguousarray(Q[:, ::-1]))
+            Qd = Qd.to(dev)[:, :bc]
+            Vr = hip_ops.svd_mul(V, Qd, out=T[:, :bc])                # V' in T
+            Yr = hip_ops.svd_mul(Y, Qd, out=S[:, :bc])                # Y' in S (V is done with)
+            res = hip_ops.svd_residuals(Yr, Vr, torch.from_numpy(theta).to(dev)).cpu().numpy()
+            residual = float(res[:k].max())
+            if residual <= self.TOL * theta[0]:
+                break
+            V = self._orth(self._orth(Yr, P, T, ws), P, S, ws)        # back in S; P and T are free
+        else:
+            raise RuntimeError(f'{self.name}.fit: no convergence in {self.MAX_ITER} iterations: residual '
+                               f'{residual:.3e} > {self.TOL * theta[0]:.3e}')
+        items = hip_ops.svd_empty(n_items, k, dev)
+        items.copy_(Vr[:, :k])
+        self.users_factors = hip_ops.svd_spmm(X, items)
+        self.items_factors = items
+        self.singular_values = np.sqrt(np.maximum(theta[:k], 0.0))
+        self.n_users, self.n_items = n_users, n_items
+        self.n_iter_, self.residual_ = it, residual
+
+    # ------------------------------------------------------------------ scoring
+    def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
+        if self.items_factors is None:
+            raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
+        u = u_idxs.to(self.device, torch.int64).contiguous()
+        if self._status is None:
+            self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return hip_ops.svd_score_rows(u, self.users_factors, self.items_factors, excl=excl, out=out,
+                                      status=self._status)
+
+    check_indices = KNNAlgorithm.check_indices
+
+    # ------------------------------------------------------------------ persistence
+    def save_model_to_path(self, path: str):
+        """The reference's two keys (mf_algs.py:51-54) plus alg, n_factors and singular_values, which its loader
+        ignores."""
+        np.savez(os.path.join(path, 'model.npz'), users_factors=self.users_factors.cpu().numpy(),
+                 items_factors=self.items_factors.cpu().numpy(), alg=np.array('svd'),
+                 n_factors=np.int64(self.n_factors), singular_values=self.singular_values)
+        logging.info('Model Saved')
+
+    def load_model_from_path(self, path: str):
+        """Reads a file written here or by the reference (no `alg` key; float32 if its svds ran on the float32 cast of
+        an integer matrix -- any float dtype is taken and held as float64)."""
+        with np.load(os.path.join(path, 'model.npz')) as f:       # never with allow_pickle
+            if 'alg' in f and str(f['alg']) != 'svd':
+                raise ValueError(f"model.npz holds a {str(f['alg'])} model, not {self.name}")
+            for key in ('users_factors', 'items_factors'):
+                if key not in f:
+                    raise ValueError(f'model.npz has no {key}')
+            try:
+                uf, vf = f['users_factors'], f['items_factors']
+            except ValueError as e:
+                raise ValueError('the factors of model.npz are object arrays; they are not unpickled') from e
+            for key, a in (('users_factors', uf), ('items_factors', vf)):
+                if a.ndim != 2 or not np.issubdtype(a.dtype, np.floating):
+                    raise ValueError(f'{key} of model.npz must be a 2-D float array, got {a.dtype} {a.shape}')
+            k = uf.shape[1]
+            if vf.shape[1] != k or not 1 <= k <= hip_ops.SVD_MAX_BLOCK or uf.shape[0] < 1 or vf.shape[0] < 1:
+                raise ValueError(f'users_factors {uf.shape} and items_factors {vf.shape} of model.npz do not share a '
+                                 f'number of factors in [1, {hip_ops.SVD_MAX_BLOCK}]')
+            if 'n_factors' in f and int(f['n_factors']) != k:
+                raise ValueError(f"n_factors = {int(f['n_factors'])} of model.npz, but the factors have {k} columns")
+            sv = None
+            if 'singular_values' in f:
+                sv = np.asarray(f['singular_values'], np.float64)
+                if sv.shape != (k,):
+                    raise ValueError(f'singular_values of model.npz has shape {sv.shape}, expected ({k},)')
+        self._forget()
+        self.n_factors, self.singular_values = k, sv
+        self.n_users, self.n_items = uf.shape[0], vf.shape[0]
+        self.users_factors, self.items_factors = self._padded(uf), self._padded(vf)
+        logging.info('Model Loaded')
+
+    def _padded(self, a: np.ndarray) -> torch.Tensor:
+        """[n, k] float64 on the device as a view of an even-stride buffer (16-byte aligned rows for any k)."""
+        buf = np.zeros((a.shape[0], hip_ops.svd_ld(a.shape[1])), np.float64)
+        buf[:, :a.shape[1]] = a
+        return torch.from_numpy(buf).to(self.device)[:, :a.shape[1]]
+
+    @staticmethod
+    def build_from_conf(conf: dict, dataset):
+        validate_svd_conf(conf)
+        return SVDAlgorithm(conf['n_factors'])

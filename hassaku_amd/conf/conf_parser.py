@@ -51,6 +51,7 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
     from hassaku_amd.algorithms.graph_algs import P3alpha, validate_p3alpha_conf
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
     from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
+    from hassaku_amd.algorithms.mf_algs import SVDAlgorithm, validate_svd_conf
     from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 
     assert 'data_path' in conf, 'Data path is missing from the configuration file'
@@ -61,6 +62,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
         validate_ease_conf(conf)
     elif issubclass(alg.value, P3alpha):
         validate_p3alpha_conf(conf)
+    elif issubclass(alg.value, SVDAlgorithm):
+        validate_svd_conf(conf)
     conf['alg'] = alg.name
     conf['time_run'] = generate_id()
     conf['dataset'] = dataset.name

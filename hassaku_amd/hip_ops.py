@@ -1016,3 +1016,150 @@ def p3_score_rows(users: torch.Tensor, x_csr, W: torch.Tensor, inv_deg_u: torch.
                                      float(alpha), max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1],
                                      _p(status), _stream()), 'hsk_p3_score_rows')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# SVD (hsk_svd.hip)
+# ---------------------------------------------------------------------------------------------------
+SVD_MAX_BLOCK = 512    # HSK_SVD_MAX_BLOCK: a wider block is refused by the library (error code), not here
+
+
+def svd_ld(b: int) -> int:
+    """The leading dimension of a freshly allocated block of width b: b rounded up to even."""
+    return int(b) + (int(b) & 1)
+
+
+def svd_empty(n: int, b: int, device) -> torch.Tensor:
+    """An uninitialised fp64 [n, b] block whose rows are 16-byte aligned (a view of an [n, svd_ld(b)] buffer)."""
+    return torch.empty((n, svd_ld(b)), dtype=torch.float64, device=device)[:, :b]
+
+
+def _svd_dense(t: torch.Tensor, name: str, even: bool = True):
+    """(rows, width, ld) of a row-major fp64 block: a 2-D tensor, or a column slice [:, :b] of one, on the device,
+    16-byte aligned, with unit column stride and (if `even`) an even row stride >= its width."""
+    if t is None:
+        raise ValueError(f'{name} must not be None')
+    if not t.is_cuda:
+        raise RuntimeError(f'{name} must live on the HIP device (got {t.device}); there is no CPU path')
+    if t.dtype != torch.float64:
+        raise TypeError(f'{name} must be torch.float64, got {t.dtype}')
+    if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f'{name} has shape {tuple(t.shape)}, expected a non-empty 2-D block')
+    rows, width = t.shape
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), svd_ld(width) if even else width)
+    if t.stride(1) != 1 or ld < width or (even and ld % 2):
+        raise ValueError(f'{name} (strides {t.stride()}) must be row-major with a'
+                         f'{"n even" if even else ""} leading dimension >= {width}')
+    if even and t.data_ptr() % 16:
+        raise ValueError(f'{name} must be 16-byte aligned')
+    return rows, width, ld
+
+
+def svd_spmm(csr, V: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [n_rows, b]: CSR @ V with every stored entry 1, each sum in stored order from 0.0 (bitwise scipy's
+    csr @ dense).  csr: (indptr int64 [n_rows + 1], indices int32, n_cols); V [n_cols, b]."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    ptr, idx, n_cols = csr
+    n_rows = ptr.numel() - 1
+    _chk(ptr, torch.int64, 'indptr', (n_rows + 1,))
+    _chk(idx, torch.int32, 'indices')
+    vr, b, ldv = _svd_dense(V, 'V')
+    if vr != n_cols or n_rows < 1:
+        raise ValueError(f'V has {vr} rows, the CSR {n_cols} columns and {n_rows} rows')
+    if out is None:
+        out = svd_empty(n_rows, b, V.device)
+    orr, ob, ldo = _svd_dense(out, 'out')
+    if (orr, ob) != (n_rows, b):
+        raise ValueError(f'out has shape {tuple(out.shape)}, expected ({n_rows}, {b})')
+    _lib.check(lib.hsk_svd_spmm_f64(_p(ptr), _p(idx), n_rows, n_cols, _p(V), ldv, b, _p(out), ldo, _stream()),
+               'hsk_svd_spmm_f64')
+    return out
+
+
+def svd_gram_ws_bytes(n: int, b: int) -> int:
+    return int(_lib.load().hsk_svd_gram_ws_bytes(int(n), int(b)))
+
+
+def svd_gram(A: torch.Tensor, B: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [b, b]: A^T B (B = A if not given) of two [n, b] blocks on the fp64 matrix cores; bitwise equal from call
+    to call.  ws: a contiguous fp64 workspace of at least svd_gram_ws_bytes(n, b) bytes (allocated if not given)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    B = A if B is None else B
+    n, b, lda = _svd_dense(A, 'A')
+    nb, bb, ldb = _svd_dense(B, 'B')
+    if (nb, bb) != (n, b):
+        raise ValueError(f'A {tuple(A.shape)} and B {tuple(B.shape)} differ in shape')
+    need = svd_gram_ws_bytes(n, b)
+    if ws is None:
+        ws = torch.empty(max(need // 8, 2), dtype=torch.float64, device=A.device)
+    _chk(ws, torch.float64, 'ws')
+    if ws.numel() * 8 < need or ws.data_ptr() % 16:
+        raise ValueError(f'ws holds {ws.numel() * 8} bytes, svd_gram needs {need}, 16-byte aligned')
+    H = torch.empty((b, b), dtype=torch.float64, device=A.device)
+    _lib.check(lib.hsk_svd_gram_f64(_p(A), lda, _p(B), ldb, n, b, _p(H), b, _p(ws), ws.numel() * 8, _stream()),
+               'hsk_svd_gram_f64')
+    return H
+
+
+def svd_mul(A: torch.Tensor, Q: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [n, b2]: A Q with A [n, b], Q [b, b2], b2 <= b, on the fp64 matrix cores; out must not be A."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    n, b, lda = _svd_dense(A, 'A')
+    qr, b2, ldq = _svd_dense(Q, 'Q')
+    if qr != b or b2 > b:
+        raise ValueError(f'Q has shape {tuple(Q.shape)}, expected ({b}, b2 <= {b})')
+    if out is None:
+        out = svd_empty(n, b2, A.device)
+    orr, ob, ldo = _svd_dense(out, 'out', even=False)
+    if (orr, ob) != (n, b2):
+        raise ValueError(f'out has shape {tuple(out.shape)}, expected ({n}, {b2})')
+    if out.data_ptr() == A.data_ptr():
+        raise ValueError('svd_mul is not in place: out must not be A')
+    _lib.check(lib.hsk_svd_mul_f64(_p(A), lda, n, b, _p(Q), ldq, b2, _p(out), ldo, _stream()), 'hsk_svd_mul_f64')
+    return out
+
+
+def svd_residuals(Y: torch.Tensor, V: torch.Tensor, theta: torch.Tensor) -> torch.Tensor:
+    """fp64 [b]: || Y[:, j] - theta[j] V[:, j] ||_2 of two [n, b] blocks (theta = 0: the column norms of Y)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    n, b, ldy = _svd_dense(Y, 'Y')
+    nv, bv, ldv = _svd_dense(V, 'V')
+    if (nv, bv) != (n, b):
+        raise ValueError(f'Y {tuple(Y.shape)} and V {tuple(V.shape)} differ in shape')
+    _chk(theta, torch.float64, 'theta', (b,))
+    res = torch.empty(b, dtype=torch.float64, device=Y.device)
+    _lib.check(lib.hsk_svd_residuals_f64(_p(Y), ldy, _p(V), ldv, _p(theta), n, b, _p(res), _stream()),
+               'hsk_svd_residuals_f64')
+    return res
+
+
+def svd_score_rows(users: torch.Tensor, UF: torch.Tensor, IF: torch.Tensor, excl=None,
+                   out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [R, n_items]: row q = UF[users[q]] @ IF^T (UF [n_users, k], IF [n_items, k]) on the fp64 matrix cores;
+    excl: (indptr, indices) -> those columns -inf."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(users, torch.int64, 'users')
+    R = users.numel()
+    n_users, k, ldu = _svd_dense(UF, 'UF')
+    n_items, ki, ldi = _svd_dense(IF, 'IF')
+    if ki != k:
+        raise ValueError(f'UF {tuple(UF.shape)} and IF {tuple(IF.shape)} differ in the number of factors')
+    ep, ei = excl if excl is not None else (None, None)
+    if excl is not None:
+        _chk(ep, torch.int64, 'excl_indptr')
+        _chk(ei, torch.int32, 'excl_indices')
+    if out is None:
+        out = torch.empty((R, n_items), dtype=torch.float64, device=users.device)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_items:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_items})')
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    _lib.check(lib.hsk_svd_score_rows(_p(users), R, n_users, _p(UF), ldu, _p(IF), ldi, n_items, k, _p(ep), _p(ei),
+                                      _p(out), out.shape[1], _p(status), _stream()), 'hsk_svd_score_rows')
+    return out

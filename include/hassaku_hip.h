@@ -767,6 +767,51 @@ int hsk_p3_score_rows(const int64_t* users, int64_t n_rows, int64_t n_users, con
                       double alpha, int64_t window, const int64_t* excl_indptr, const int32_t* excl_indices, double* out,
                       int64_t ld, int32_t* status, hsk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SVD (algorithms/mf_algs.py:13-65): the leading n_factors singular triplets of the binary train matrix X by block
+ * subspace iteration with Rayleigh-Ritz on X^T X (never formed).  All fp64.  Every dense operand is row-major and
+ * 16-byte aligned with an even leading dimension >= its width; a block width b (or k) outside
+ * [1, HSK_SVD_MAX_BLOCK] is refused with HSK_ERR_INVALID.  Any width in range works, not only multiples of 16.
+ * ------------------------------------------------------------------------------------------ */
+
+#define HSK_SVD_MAX_BLOCK 512
+
+/* out[r, c] = ((0.0 + V[i1, c]) + V[i2, c]) + ... for c < b over the column ids i1, i2, ... of row r of the CSR
+ * (indptr int64 [n_rows + 1], indices int32, every stored entry = 1) in stored order: scipy's csr @ dense order, so the
+ * result is bitwise scipy's.  V is n_cols x b (leading dimension ldv), out n_rows x b (ldo).  An empty row gives +0.0;
+ * an id outside [0, n_cols) is skipped; the columns in [b, ldo) are never written.  One wave per (row, 128 columns). */
+int hsk_svd_spmm_f64(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols, const double* V,
+                     int64_t ldv, int64_t b, double* out, int64_t ldo, hsk_stream_t stream);
+
+/* bytes of the workspace of hsk_svd_gram_f64: one b x b partial per row split (0 for a shape it refuses) */
+int64_t hsk_svd_gram_ws_bytes(int64_t n, int64_t b);
+
+/* H[i, j] = sum_r A[r, i] * B[r, j] for i, j < b, A and B n x b (B may be A), on v_mfma_f64_16x16x4_f64.  The grid is
+ * (64 x 64 tiles of H) x (row splits); every split writes its partial to the workspace and a second kernel adds the
+ * partials in ascending split order: no floating-point atomics, so two calls give bitwise equal results.  H has
+ * leading dimension ldh >= b (any parity).  workspace: device memory, 16-byte aligned, workspace_bytes >=
+ * hsk_svd_gram_ws_bytes(n, b). */
+int hsk_svd_gram_f64(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t n, int64_t b, double* H,
+                     int64_t ldh, void* workspace, int64_t workspace_bytes, hsk_stream_t stream);
+
+/* out[r, j] = sum_i A[r, i] * Q[i, j] for r < n, j < b2: A n x b, Q b x b2 with 1 <= b2 <= b, out n x b2 (leading
+ * dimension ldo >= b2, any parity), out distinct from A.  fp64 MFMA with the blocks of Q staged in LDS. */
+int hsk_svd_mul_f64(const double* A, int64_t lda, int64_t n, int64_t b, const double* Q, int64_t ldq, int64_t b2,
+                    double* out, int64_t ldo, hsk_stream_t stream);
+
+/* res[j] = || Y[:, j] - theta[j] * V[:, j] ||_2 for j < b over n rows; every column's partial sums of squares are
+ * added in a fixed order (bitwise equal from run to run).  theta = 0 gives the column norms of Y. */
+int hsk_svd_residuals_f64(const double* Y, int64_t ldy, const double* V, int64_t ldv, const double* theta, int64_t n,
+                          int64_t b, double* res, hsk_stream_t stream);
+
+/* fp64 score rows of a factor model (mf_algs.py:41-49): out[q, j] = sum_f UF[users[q], f] * IF[j, f] for f < k on the
+ * fp64 matrix cores; UF n_users x k (ldu), IF n_items x k (ldi), out n_rows x n_items (ld >= n_items).  excl_indptr /
+ * excl_indices and *status as in hsk_ease_score_rows: excluded columns come back as -inf, an out-of-range user id
+ * sets HSK_STATUS_BAD_INDEX and reads row 0. */
+int hsk_svd_score_rows(const int64_t* users, int64_t n_rows, int64_t n_users, const double* UF, int64_t ldu,
+                       const double* IF, int64_t ldi, int64_t n_items, int64_t k, const int64_t* excl_indptr,
+                       const int32_t* excl_indices, double* out, int64_t ld, int32_t* status, hsk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
