@@ -21,8 +21,7 @@ import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import SparseMatrixBasedRecommenderAlgorithm
-from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, _csr_arrays, _transpose
+from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays
 
 
 def _alpha(alpha) -> float:
@@ -42,21 +41,16 @@ def validate_p3alpha_conf(conf: dict):
     _alpha(conf['alpha'])
 
 
-class P3alpha(SparseMatrixBasedRecommenderAlgorithm):
+class P3alpha(FittedRecommenderAlgorithm):
     GRAM_BLOCK_ROWS = 4096       # rows of W per launch of the Gram kernel (a multiple of 128)
     WINDOW = 1024                # item window of one scoring workgroup
 
     def __init__(self, alpha=1.9, device='cuda'):
-        super().__init__()
+        super().__init__(device)
         self.alpha = _alpha(alpha)
-        self.device = torch.device(device)
         self.name = 'P3alpha'
-        self.pred_mtx = None       # dense float64 predictions of a reference-style model.npz
         self.W = None              # fp64 [n_items, n_items] on the device
         self.inv_deg_u = None      # fp64 [n_users]: 1 / user degree, 0 for users without items
-        self.train = None          # (indptr int64, indices int32) of X
-        self.n_users = self.n_items = None
-        self._status = None
         logging.info('Built %s: alpha %s', self.name, self.alpha)
 
     # ------------------------------------------------------------------ fit
@@ -66,15 +60,11 @@ class P3alpha(SparseMatrixBasedRecommenderAlgorithm):
         return 8 * n_items * n_items + rows_pad * k_pad + 8 * (k_pad + n_items)
 
     def fit(self, matrix):
-        indptr, indices, n_users, n_items = _csr_arrays(matrix)
+        indptr, indices, n_users, n_items = csr_arrays(matrix)
         dev = self.device
-        need = self.fit_bytes(n_users, n_items)
-        free = torch.cuda.mem_get_info(dev)[0]
-        if need > free:
-            raise ValueError(f'P3alpha.fit on {n_items} items needs {need} bytes of device memory, {free} are free')
+        self._require_free(self.fit_bytes(n_users, n_items), f'{n_items} items')
         self.W = self.pred_mtx = self.inv_deg_u = None     # a fit that raises leaves no model behind
-        x_ptr, x_idx = torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev)
-        t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n_items)
+        x_ptr, x_idx, t_ptr, t_idx = self._upload(indptr, indices, transpose=(n_users, n_items))
         M = hip_ops.knn_pack_i8(t_ptr, t_idx, n_items, n_users)
         w_u = hip_ops.p3_inv_degrees(x_ptr, M.shape[1])     # zero on the padding of k
         w_i = hip_ops.p3_inv_degrees(t_ptr)
@@ -90,23 +80,14 @@ class P3alpha(SparseMatrixBasedRecommenderAlgorithm):
         return self.W.cpu().numpy()
 
     # ------------------------------------------------------------------ scoring
-    _dense_rows = KNNAlgorithm._dense_rows
-
     def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
         u = u_idxs.to(self.device, torch.int64).contiguous()
         if self.pred_mtx is not None:
             return self._dense_rows(u, excl)
         if self.W is None:
             raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
-        if self._status is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
         return hip_ops.p3_score_rows(u, (*self.train, self.n_users), self.W, self.inv_deg_u, self.alpha,
-                                     window=self.WINDOW, excl=excl, out=out, status=self._status)
-
-    def check_indices(self):
-        if self._status is not None and int(self._status.item()) != 0:
-            self._status.zero_()
-            raise IndexError(f'{self.name}: user index outside [0, {self.n_users})')
+                                     window=self.WINDOW, excl=excl, out=out, status=self._status_word())
 
     # ------------------------------------------------------------------ persistence
     def save_model_to_path(self, path: str):
@@ -115,46 +96,44 @@ class P3alpha(SparseMatrixBasedRecommenderAlgorithm):
                  train_indptr=self.train[0].cpu().numpy(), train_indices=self.train[1].cpu().numpy())
         logging.info('Model Saved')
 
+    @staticmethod
+    def _read_pred_mtx(f) -> np.ndarray:
+        try:
+            pred = f['pred_mtx']
+        except ValueError as e:
+            # graph_algs.py:74-77 hands np.savez its scipy sparse pred_mtx, which numpy pickles as an object
+            # array; the reference's own np.load (graph_algs.py:79-83) cannot read that back either
+            raise ValueError('pred_mtx of model.npz is an object array (the pickled sparse matrix the '
+                             "reference's P3alpha writes and cannot read back itself); it is not loaded: "
+                             'save the dense rows (pred_mtx.toarray()) instead') from e
+        if pred.dtype == object:
+            raise ValueError('pred_mtx of model.npz is an object array (the pickled sparse matrix the '
+                             "reference's P3alpha writes and cannot read back itself); it is not loaded")
+        if pred.ndim != 2 or not np.issubdtype(pred.dtype, np.floating):
+            raise ValueError('pred_mtx of model.npz must be a dense 2-D float array')
+        return pred
+
     def load_model_from_path(self, path: str):
         dev = self.device
         with np.load(os.path.join(path, 'model.npz')) as f:       # never with allow_pickle
             if 'pred_mtx' in f:
-                try:
-                    pred = f['pred_mtx']
-                except ValueError as e:
-                    # graph_algs.py:74-77 hands np.savez its scipy sparse pred_mtx, which numpy pickles as an object
-                    # array; the reference's own np.load (graph_algs.py:79-83) cannot read that back either
-                    raise ValueError('pred_mtx of model.npz is an object array (the pickled sparse matrix the '
-                                     "reference's P3alpha writes and cannot read back itself); it is not loaded: "
-                                     'save the dense rows (pred_mtx.toarray()) instead') from e
-                if pred.dtype == object:
-                    raise ValueError('pred_mtx of model.npz is an object array (the pickled sparse matrix the '
-                                     "reference's P3alpha writes and cannot read back itself); it is not loaded")
-                if pred.ndim != 2 or not np.issubdtype(pred.dtype, np.floating):
-                    raise ValueError('pred_mtx of model.npz must be a dense 2-D float array')
-                self.pred_mtx = torch.from_numpy(np.ascontiguousarray(pred, np.float64)).to(dev)
-                self.n_users, self.n_items = pred.shape
-                self.W = self.train = self.inv_deg_u = None
+                self._load_pred_mtx(f)
+                self.W = self.inv_deg_u = None
             else:
-                alg = str(f['alg'])
-                if alg != 'p3alpha':
-                    raise ValueError(f'model.npz holds a {alg} model, not {self.name}')
+                self._check_alg(f, 'p3alpha')
                 n_users, n_items = int(f['n_users']), int(f['n_items'])
                 alpha = _alpha(float(f['alpha']))
-                W, t_ptr, t_idx = f['W'], f['train_indptr'], f['train_indices']
+                W = f['W']
                 if W.shape != (n_items, n_items):
                     raise ValueError(f'W of model.npz has shape {W.shape}, expected ({n_items}, {n_items})')
-                if (t_ptr.shape != (n_users + 1,) or t_ptr[0] != 0 or np.any(np.diff(t_ptr) < 0) or
-                        t_ptr[-1] != len(t_idx) or (len(t_idx) and not (0 <= t_idx.min() and t_idx.max() < n_items))):
-                    raise ValueError(f'train CSR of model.npz does not describe {n_users} users x {n_items} items')
-                deg = np.diff(np.asarray(t_ptr, np.int64))
+                t_ptr, t_idx = self._read_train(f, n_users, n_items)
+                deg = np.diff(t_ptr)
                 w_u = np.zeros(n_users, np.float64)
                 w_u[deg > 0] = 1.0 / deg[deg > 0]        # one IEEE division each, as hsk_p3_inv_degrees
                 self.n_users, self.n_items, self.alpha = n_users, n_items, alpha
                 self.W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(dev)
                 self.inv_deg_u = torch.from_numpy(w_u).to(dev)
-                self.train = (torch.from_numpy(np.ascontiguousarray(t_ptr, np.int64)).to(dev),
-                              torch.from_numpy(np.ascontiguousarray(t_idx, np.int32)).to(dev))
+                self.train = self._upload(t_ptr, t_idx)
                 self.pred_mtx = None
         logging.info('Model Loaded')
 

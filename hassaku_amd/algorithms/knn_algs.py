@@ -17,8 +17,7 @@ import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import SparseMatrixBasedRecommenderAlgorithm
-from hassaku_amd.data.csr import UserItemCsr
+from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays, csr_transpose
 
 
 class SimilarityFunctionEnum(Enum):
@@ -57,28 +56,10 @@ def validate_knn_conf(conf: dict):
         raise ValueError(f'shrinkage = {shrinkage!r} must be a number >= 0')
 
 
-def _csr_arrays(matrix):
-    """(indptr int64, indices int32, n_rows, n_cols) of a UserItemCsr or a scipy sparse matrix (stored entries = 1)."""
-    if isinstance(matrix, UserItemCsr):
-        return (np.ascontiguousarray(matrix.indptr, np.int64), np.ascontiguousarray(matrix.indices, np.int32),
-                matrix.n_rows, matrix.n_cols)
-    m = matrix.tocsr(copy=True)
-    m.sum_duplicates()
-    m.eliminate_zeros()
-    m.sort_indices()
-    return (m.indptr.astype(np.int64), m.indices.astype(np.int32), m.shape[0], m.shape[1])
+_transpose = csr_transpose     # the name this module had it under; tests/test_ease.py and test_p3alpha.py import it
 
 
-def _transpose(indptr, indices, vals, n_rows, n_cols):
-    """CSR of the transpose on the device, each row's entries in ascending column order."""
-    rows = torch.repeat_interleave(torch.arange(n_rows, device=indptr.device), indptr[1:] - indptr[:-1])
-    order = torch.argsort(indices.long() * n_rows + rows)
-    t_ptr = torch.zeros(n_cols + 1, dtype=torch.int64, device=indptr.device)
-    torch.cumsum(torch.bincount(indices.long(), minlength=n_cols), 0, out=t_ptr[1:])
-    return t_ptr, rows[order].to(torch.int32).contiguous(), None if vals is None else vals[order].contiguous()
-
-
-class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
+class KNNAlgorithm(FittedRecommenderAlgorithm):
     """Common part of UserKNN / ItemKNN (knn_algs.py:13-72)."""
     GRAM_BLOCK_BYTES = 1 << 30   # int32 counts of one row block
     WINDOW = 4096                # item window of one scoring wave (fp64 accumulators in LDS)
@@ -86,7 +67,7 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
 
     def __init__(self, sim_func_enum: SimilarityFunctionEnum = SimilarityFunctionEnum.cosine, k: int = 100,
                  shrinkage: float = .0, device='cuda', **kwargs):
-        super().__init__()
+        super().__init__(device)
         if isinstance(sim_func_enum, str):
             sim_func_enum = SimilarityFunctionEnum[sim_func_enum]
         for key in _needs(sim_func_enum):
@@ -97,27 +78,18 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
         self.sim_func_enum = sim_func_enum
         self.alpha, self.beta = kwargs.get('alpha'), kwargs.get('beta')
         self.k, self.shrinkage = int(k), float(shrinkage)
-        self.device = torch.device(device)
         self.name = 'KNNAlgorithm'
-        self.pred_mtx = None       # dense float64 predictions of a reference-written model.npz
         self.neigh = None          # (indptr int64, indices int32, vals fp64) of S, stored order
-        self.train = None          # (indptr int64, indices int32) of X
-        self.n_users = self.n_items = None
         self._b_t = None           # S^T (ItemKNN scoring)
-        self._status = None
         logging.info('Built %s: sim_func %s, k %d, shrinkage %s', self.name, sim_func_enum.name, self.k, self.shrinkage)
 
     # ------------------------------------------------------------------ fit
     def fit(self, matrix):
-        indptr, indices, n_users, n_items = _csr_arrays(matrix)
+        indptr, indices, n_users, n_items = csr_arrays(matrix)
         dev = self.device
-        x_ptr, x_idx = torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev)
-        self.train, self.n_users, self.n_items = (x_ptr, x_idx), n_users, n_items
-        if self.ITEM_BASED:
-            e_ptr, e_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n_items)
-            n_ent, n_feat = n_items, n_users
-        else:
-            e_ptr, e_idx, n_ent, n_feat = x_ptr, x_idx, n_users, n_items
+        up = self._upload(indptr, indices, transpose=(n_users, n_items) if self.ITEM_BASED else None)
+        self.train, self.n_users, self.n_items = up[:2], n_users, n_items
+        (e_ptr, e_idx), (n_ent, n_feat) = up[-2:], (n_items, n_users) if self.ITEM_BASED else (n_users, n_items)
         deg = np.diff(e_ptr.cpu().numpy()).astype(np.int64)
         sim = self.sim_func_enum
         put = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)  # noqa: E731
@@ -157,7 +129,7 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
         x_ptr, x_idx = self.train
         if self.ITEM_BASED:          # pred = X S^T: the user's items in ascending order pick rows of S^T
             if self._b_t is None:
-                self._b_t = _transpose(s_ptr, s_idx, s_val, self.n_items, self.n_items)
+                self._b_t = csr_transpose(s_ptr, s_idx, s_val, self.n_items, self.n_items)
             return (x_ptr, x_idx, None, self.n_users), (*self._b_t, self.n_items)
         return (s_ptr, s_idx, s_val, self.n_users), (x_ptr, x_idx, None, self.n_users)   # pred = S X
 
@@ -167,27 +139,9 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
             return self._dense_rows(u, excl)
         if self.neigh is None:
             raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
-        if self._status is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
         a, b = self._operands()
         return hip_ops.knn_score_rows(u, a, b, self.n_items, window=self.WINDOW, excl=excl, out=out,
-                                      status=self._status)
-
-    def _dense_rows(self, u, excl):
-        rows = self.pred_mtx[u]
-        if excl is not None:
-            ep, ei = excl
-            lens = ep[u + 1] - ep[u]
-            which = torch.repeat_interleave(torch.arange(len(u), device=u.device), lens)
-            starts = torch.repeat_interleave(ep[u] - (torch.cumsum(lens, 0) - lens), lens)
-            cols = ei[starts + torch.arange(int(lens.sum()), device=u.device)].long()
-            rows[which, cols] = -torch.inf
-        return rows.contiguous()
-
-    def check_indices(self):
-        if self._status is not None and int(self._status.item()) != 0:
-            self._status.zero_()
-            raise IndexError(f'{self.name}: user index outside [0, {self.n_users})')
+                                      status=self._status_word())
 
     # ------------------------------------------------------------------ persistence
     def save_model_to_path(self, path: str):
@@ -202,21 +156,16 @@ class KNNAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
         dev = self.device
         with np.load(os.path.join(path, 'model.npz')) as f:
             if 'pred_mtx' in f:       # written by the reference (knn_algs.py:46-56): dense float64 predictions
-                pred = f['pred_mtx']
-                if pred.ndim != 2:
-                    raise ValueError('pred_mtx of model.npz must be a dense 2-D array')
-                self.pred_mtx = torch.from_numpy(np.ascontiguousarray(pred, np.float64)).to(dev)
-                self.n_users, self.n_items = pred.shape
-                self.neigh = self.train = self._b_t = None
+                self._load_pred_mtx(f)
+                self.neigh = None
             else:
-                alg = str(f['alg'])
-                if alg != ('iknn' if self.ITEM_BASED else 'uknn'):
-                    raise ValueError(f'model.npz holds a {alg} model, not {self.name}')
+                self._check_alg(f, 'iknn' if self.ITEM_BASED else 'uknn')
                 self.n_users, self.n_items = int(f['n_users']), int(f['n_items'])
                 self.neigh = (torch.from_numpy(f['neigh_indptr']).to(dev), torch.from_numpy(f['neigh_indices']).to(dev),
                               torch.from_numpy(f['neigh_data']).to(dev))
-                self.train = (torch.from_numpy(f['train_indptr']).to(dev), torch.from_numpy(f['train_indices']).to(dev))
-                self.pred_mtx, self._b_t = None, None
+                self.train = self._upload(*self._read_train(f, self.n_users, self.n_items, validate=False))
+                self.pred_mtx = None
+            self._b_t = None
         logging.info('Model Loaded')
 
     @staticmethod

@@ -18,8 +18,7 @@ import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import SparseMatrixBasedRecommenderAlgorithm
-from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, _csr_arrays, _transpose
+from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays
 
 
 def _lam_int(lam) -> int:
@@ -39,21 +38,16 @@ def validate_ease_conf(conf: dict):
     _lam_int(conf['lam'])
 
 
-class EASE(SparseMatrixBasedRecommenderAlgorithm):
+class EASE(FittedRecommenderAlgorithm):
     GRAM_BLOCK_BYTES = 1 << 30   # int32 counts of one row block
     WINDOW = 1024                # item window of one scoring workgroup
 
     def __init__(self, lam, device='cuda'):
-        super().__init__()
+        super().__init__(device)
         self.lam = lam
         self.lam_int = _lam_int(lam)
-        self.device = torch.device(device)
         self.name = 'EASE'
-        self.pred_mtx = None       # dense float64 predictions of a reference-written model.npz
         self.B = None              # fp64 [n_items, n_items] on the device
-        self.train = None          # (indptr int64, indices int32) of X
-        self.n_users = self.n_items = None
-        self._status = None
         logging.info('Built %s: lam %s (int %d)', self.name, lam, self.lam_int)
 
     # ------------------------------------------------------------------ fit
@@ -68,15 +62,11 @@ class EASE(SparseMatrixBasedRecommenderAlgorithm):
                 hip_ops.ease_inverse_ws_bytes(n_items))
 
     def fit(self, matrix):
-        indptr, indices, n_users, n_items = _csr_arrays(matrix)
+        indptr, indices, n_users, n_items = csr_arrays(matrix)
         dev = self.device
-        need = self.fit_bytes(n_users, n_items)
-        free = torch.cuda.mem_get_info(dev)[0]
-        if need > free:
-            raise ValueError(f'EASE.fit on {n_items} items needs {need} bytes of device memory, {free} are free')
+        self._require_free(self.fit_bytes(n_users, n_items), f'{n_items} items')
         self.B = self.pred_mtx = None     # a fit that raises leaves no model behind, not the old B on a new matrix
-        x_ptr, x_idx = torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev)
-        t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n_items)
+        x_ptr, x_idx, t_ptr, t_idx = self._upload(indptr, indices, transpose=(n_users, n_items))
         M = hip_ops.knn_pack_i8(t_ptr, t_idx, n_items, n_users)
         block = self._gram_block(n_items)
         C = torch.empty((block, n_items), dtype=torch.int32, device=dev)
@@ -95,23 +85,14 @@ class EASE(SparseMatrixBasedRecommenderAlgorithm):
         return self.B.cpu().numpy()
 
     # ------------------------------------------------------------------ scoring
-    _dense_rows = KNNAlgorithm._dense_rows
-
     def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
         u = u_idxs.to(self.device, torch.int64).contiguous()
         if self.pred_mtx is not None:
             return self._dense_rows(u, excl)
         if self.B is None:
             raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
-        if self._status is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
         return hip_ops.ease_score_rows(u, (*self.train, self.n_users), self.B, window=self.WINDOW, excl=excl, out=out,
-                                       status=self._status)
-
-    def check_indices(self):
-        if self._status is not None and int(self._status.item()) != 0:
-            self._status.zero_()
-            raise IndexError(f'{self.name}: user index outside [0, {self.n_users})')
+                                       status=self._status_word())
 
     # ------------------------------------------------------------------ persistence
     def save_model_to_path(self, path: str):
@@ -121,30 +102,20 @@ class EASE(SparseMatrixBasedRecommenderAlgorithm):
         logging.info('Model Saved')
 
     def load_model_from_path(self, path: str):
-        dev = self.device
         with np.load(os.path.join(path, 'model.npz')) as f:
             if 'pred_mtx' in f:       # written by the reference (linear_algs.py:163-166): dense float64 predictions
-                pred = f['pred_mtx']
-                if pred.ndim != 2:
-                    raise ValueError('pred_mtx of model.npz must be a dense 2-D array')
-                self.pred_mtx = torch.from_numpy(np.ascontiguousarray(pred, np.float64)).to(dev)
-                self.n_users, self.n_items = pred.shape
-                self.B = self.train = None
+                self._load_pred_mtx(f)
+                self.B = None
             else:
-                alg = str(f['alg'])
-                if alg != 'ease':
-                    raise ValueError(f'model.npz holds a {alg} model, not {self.name}')
+                self._check_alg(f, 'ease')
                 n_users, n_items = int(f['n_users']), int(f['n_items'])
-                B, t_ptr, t_idx = f['B'], f['train_indptr'], f['train_indices']
+                B = f['B']
                 if B.shape != (n_items, n_items):
                     raise ValueError(f'B of model.npz has shape {B.shape}, expected ({n_items}, {n_items})')
-                if (t_ptr.shape != (n_users + 1,) or t_ptr[0] != 0 or np.any(np.diff(t_ptr) < 0) or
-                        t_ptr[-1] != len(t_idx) or (len(t_idx) and not (0 <= t_idx.min() and t_idx.max() < n_items))):
-                    raise ValueError(f'train CSR of model.npz does not describe {n_users} users x {n_items} items')
+                train = self._read_train(f, n_users, n_items)
                 self.n_users, self.n_items = n_users, n_items
-                self.B = torch.from_numpy(np.ascontiguousarray(B, np.float64)).to(dev)
-                self.train = (torch.from_numpy(np.ascontiguousarray(t_ptr, np.int64)).to(dev),
-                              torch.from_numpy(np.ascontiguousarray(t_idx, np.int32)).to(dev))
+                self.B = torch.from_numpy(np.ascontiguousarray(B, np.float64)).to(self.device)
+                self.train = self._upload(*train)
                 self.pred_mtx = None
         logging.info('Model Loaded')
 

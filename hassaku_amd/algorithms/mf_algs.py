@@ -25,8 +25,7 @@ import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import SparseMatrixBasedRecommenderAlgorithm
-from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, _csr_arrays, _transpose
+from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays
 
 
 def _n_factors(n_factors) -> int:
@@ -45,24 +44,20 @@ def validate_svd_conf(conf: dict):
     _n_factors(conf['n_factors'])
 
 
-class SVDAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
+class SVDAlgorithm(FittedRecommenderAlgorithm):
     OVERSAMPLE = 32              # columns of the block beyond n_factors (before rounding up to 16)
     TOL = 1e-11                  # residual of the n_factors leading Ritz pairs, relative to theta_1
     MAX_ITER = 1000
     SEED = 0                     # of the host-made start block
 
     def __init__(self, n_factors=100, device='cuda'):
-        super().__init__()
+        super().__init__(device)          # pred_mtx and train stay None: the factors are all a model or a file holds
         self.n_factors = _n_factors(n_factors)
-        self.device = torch.device(device)
         self.name = 'SVDAlgorithm'
-        self.pred_mtx = None          # never set: _dense_rows is not used, the factors are all a file holds
         self.users_factors = None     # fp64 [n_users, k] on the device (= U S); a view of an even-stride buffer
         self.items_factors = None     # fp64 [n_items, k]
         self.singular_values = None   # numpy float64 [k], descending (None for a model loaded from the reference)
-        self.n_users = self.n_items = None
         self.n_iter_ = self.residual_ = None
-        self._status = None
         logging.info('Built %s: n_factors %d', self.name, self.n_factors)
 
     # ------------------------------------------------------------------ fit
@@ -100,21 +95,16 @@ class SVDAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
         return hip_ops.svd_mul(Yn, torch.from_numpy(R).to(dev)[:, :int(good.sum())], out=out[:, :int(good.sum())])
 
     def fit(self, matrix):
-        indptr, indices, n_users, n_items = _csr_arrays(matrix)
+        indptr, indices, n_users, n_items = csr_arrays(matrix)
         k, dev = self.n_factors, self.device
         if not 1 <= k < min(n_users, n_items):     # what svds demands of k
             raise ValueError(f'n_factors = {k} must be in [1, min(n_users, n_items) = {min(n_users, n_items)})')
         b = self.block_width(n_users, n_items)
         if b > hip_ops.SVD_MAX_BLOCK:
             raise ValueError(f'n_factors = {k} gives a block of {b} columns, at most {hip_ops.SVD_MAX_BLOCK}')
-        need = self.fit_bytes(n_users, n_items)
-        free = torch.cuda.mem_get_info(dev)[0]
-        if need > free:
-            raise ValueError(f'{self.name}.fit on {n_users} users x {n_items} items needs {need} bytes of device '
-                             f'memory, {free} are free')
+        self._require_free(self.fit_bytes(n_users, n_items), f'{n_users} users x {n_items} items')
         self._forget()                     # a fit that raises leaves no model behind
-        x_ptr, x_idx = torch.from_numpy(indptr).to(dev), torch.from_numpy(indices).to(dev)
-        t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n_items)
+        x_ptr, x_idx, t_ptr, t_idx = self._upload(indptr, indices, transpose=(n_users, n_items))
         X, Xt = (x_ptr, x_idx, n_items), (t_ptr, t_idx, n_users)
         ld = hip_ops.svd_ld(b)
         Zbuf = torch.empty((n_users, ld), dtype=torch.float64, device=dev)
@@ -159,12 +149,8 @@ class SVDAlgorithm(SparseMatrixBasedRecommenderAlgorithm):
         if self.items_factors is None:
             raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
         u = u_idxs.to(self.device, torch.int64).contiguous()
-        if self._status is None:
-            self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
         return hip_ops.svd_score_rows(u, self.users_factors, self.items_factors, excl=excl, out=out,
-                                      status=self._status)
-
-    check_indices = KNNAlgorithm.check_indices
+                                      status=self._status_word())
 
     # ------------------------------------------------------------------ persistence
     def save_model_to_path(self, path: str):

@@ -10,8 +10,10 @@
 //                     (both [EASE_NB, n_pad], zero where r or c >= b and beyond n), so the update reads nothing it writes;
 //   k_ease_update     out = (j in K ? 0 : A_ij) - sum_c Ct[c, i] Rp[c, j] on the matrix cores; rows of K take Rp instead.
 // The update's workgroup (four waves) owns 128 x 128 outputs, wave (wm, wn) the 64 x 64 block in 4 x 4 tiles of
-// 16 x 16.  The whole inner dimension (64) of both panels sits in LDS at once: no k loop over global memory.
-#include "hsk_common.h"
+// 16 x 16 (hsk_f64_tile.h).  The whole inner dimension (64) of both panels sits in LDS at once: no k loop over global
+// memory.  The scorer is hsk_gather_score.h's plain instance.
+#include "hsk_f64_tile.h"
+#include "hsk_gather_score.h"
 
 #include <limits.h>
 
@@ -19,12 +21,7 @@
 #define EASE_TILE 128
 #define EASE_LDS_ROW 144                            // 128 doubles + 16 pad: rows k and k + 1 start 32 banks apart
 #define EASE_PANEL_LDS (EASE_NB * EASE_LDS_ROW)     // doubles of one panel image
-#define EASE_SCORE_THREADS 256
-#define EASE_SCORE_PER 4                            // columns per thread and pass of the scorer
 #define EASE_GRID_ROWS 1024                         // grid.y of the row-wise kernels; each walks its rows in that stride
-
-typedef double hsk_e_f64x4 __attribute__((ext_vector_type(4)));
-typedef double hsk_e_f64x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
 // G = (double) counts + lam on the diagonal
@@ -110,57 +107,42 @@ __global__ void __launch_bounds__(256) k_ease_update(double* __restrict__ A, int
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* sa = lds;                    // Ct[:, i0 .. i0 + 128)
   double* sb = lds + EASE_PANEL_LDS;   // Rp[:, j0 .. j0 + 128)
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
   const int64_t i0 = (int64_t)blockIdx.y * EASE_TILE, j0 = (int64_t)blockIdx.x * EASE_TILE;
-  // f64 16x16x4 C/D map: column = lane & 15, row = (lane >> 4) + 4 v
-  hsk_e_f64x4 acc[4][4];
+  hsk_f64x4 acc[4][4];
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int nj = 0; nj < 4; ++nj) {
-      const int64_t gj = j0 + wn * 64 + nj * 16 + lc;
+      const int64_t gj = hsk_f64_tile_col(j0 + wn * 64, nj, lane);
       const bool col_k = gj >= k0 && gj < k0 + b;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int64_t gi = i0 + wm * 64 + mi * 16 + lq + 4 * v;
+        const int64_t gi = hsk_f64_tile_row(i0 + wm * 64, mi, v, lane);
         acc[mi][nj][v] = (gi < n && gj < n && !col_k) ? A[gi * ld + gj] : 0.0;
       }
     }
   for (int t = tid; t < EASE_NB * (EASE_TILE / 2); t += 256) {
     const int k = t / (EASE_TILE / 2), c = (t % (EASE_TILE / 2)) * 2;
-    *reinterpret_cast<hsk_e_f64x2*>(sa + k * EASE_LDS_ROW + c) =
-        *reinterpret_cast<const hsk_e_f64x2*>(Ct + k * n_pad + i0 + c);
-    *reinterpret_cast<hsk_e_f64x2*>(sb + k * EASE_LDS_ROW + c) =
-        *reinterpret_cast<const hsk_e_f64x2*>(Rp + k * n_pad + j0 + c);
+    *reinterpret_cast<hsk_f64x2*>(sa + k * EASE_LDS_ROW + c) =
+        *reinterpret_cast<const hsk_f64x2*>(Ct + k * n_pad + i0 + c);
+    *reinterpret_cast<hsk_f64x2*>(sb + k * EASE_LDS_ROW + c) =
+        *reinterpret_cast<const hsk_f64x2*>(Rp + k * n_pad + j0 + c);
   }
   __syncthreads();
-  // A operand: lane holds A[row = lane & 15][k = lane >> 4]; B operand: B[k = lane >> 4][col = lane & 15].
-  // The product is subtracted: the A operand is negated once when it is read.
-#pragma unroll 4
-  for (int ks = 0; ks < EASE_NB / 4; ++ks) {
-    double af[4], bf[4];
-    const int k = ks * 4 + lq;
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) af[mi] = -sa[k * EASE_LDS_ROW + wm * 64 + mi * 16 + lc];
-#pragma unroll
-    for (int nj = 0; nj < 4; ++nj) bf[nj] = sb[k * EASE_LDS_ROW + wn * 64 + nj * 16 + lc];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-      for (int nj = 0; nj < 4; ++nj)
-        acc[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[mi], bf[nj], acc[mi][nj], 0, 0, 0);
-  }
+  // the product is subtracted: the A operand is negated as it is read
+  hsk_f64_tile_mma<4, EASE_NB, EASE_LDS_ROW, 4, true>(acc, sa, wm * 64, sb, wn * 64, lane);
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
     for (int nj = 0; nj < 4; ++nj) {
-      const int cj = wn * 64 + nj * 16 + lc;
+      const int cj = hsk_f64_tile_col(wn * 64, nj, lane);
       const int64_t gj = j0 + cj;
       if (gj >= n) continue;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
-        const int64_t gi = i0 + wm * 64 + mi * 16 + lq + 4 * v;
+        const int64_t gi = hsk_f64_tile_row(i0 + wm * 64, mi, v, lane);
         if (gi >= n) continue;
         const bool row_k = gi >= k0 && gi < k0 + b;
         A[gi * ld + gj] = row_k ? sb[(int)(gi - k0) * EASE_LDS_ROW + cj] : acc[mi][nj][v];
@@ -183,54 +165,6 @@ __global__ void __launch_bounds__(256) k_ease_weights(double* __restrict__ P, in
   if (j >= n) return;
   const double d = nd[j];
   for (int64_t i = blockIdx.y; i < n; i += gridDim.y) P[i * ld + j] = (i == j) ? 0.0 : P[i * ld + j] / d;
-}
-
-// ---------------------------------------------------------------------------------------------
-// scoring: out[q, j] = ((0 + B[i1, j]) + B[i2, j]) + ... over the items of user users[q] in stored (ascending) order;
-// one workgroup per (user, column window), EASE_SCORE_PER columns per thread and pass
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(EASE_SCORE_THREADS) k_ease_score(
-    const int64_t* __restrict__ users, int64_t n_users, const int64_t* __restrict__ x_ptr,
-    const int32_t* __restrict__ x_idx, const double* __restrict__ B, int64_t n_items, int64_t ldb, int64_t window,
-    const int64_t* __restrict__ e_ptr, const int32_t* __restrict__ e_idx, double* __restrict__ out, int64_t ld,
-    int32_t* __restrict__ status) {
-#pragma clang fp contract(off)
-  const int tid = threadIdx.x;
-  const int64_t q = blockIdx.y, w0 = (int64_t)blockIdx.x * window;
-  const int64_t w1 = w0 + window < n_items ? w0 + window : n_items;
-  int64_t u = users[q];
-  if (u < 0 || u >= n_users) {
-    if (tid == 0) atomicOr(status, HSK_STATUS_BAD_INDEX);
-    u = 0;
-  }
-  const int64_t lo = x_ptr[u], hi = x_ptr[u + 1];
-  for (int64_t c0 = w0; c0 < w1; c0 += EASE_SCORE_THREADS * EASE_SCORE_PER) {
-    double acc[EASE_SCORE_PER];
-    int64_t col[EASE_SCORE_PER];
-#pragma unroll
-    for (int s = 0; s < EASE_SCORE_PER; ++s) {
-      acc[s] = 0.0;
-      col[s] = c0 + s * EASE_SCORE_THREADS + tid;
-    }
-    for (int64_t e = lo; e < hi; ++e) {
-      const int32_t i = x_idx[e];
-      if (i < 0 || i >= n_items) continue;
-      const double* row = B + (int64_t)i * ldb;
-#pragma unroll
-      for (int s = 0; s < EASE_SCORE_PER; ++s)
-        if (col[s] < w1) acc[s] = acc[s] + row[col[s]];
-    }
-#pragma unroll
-    for (int s = 0; s < EASE_SCORE_PER; ++s)
-      if (col[s] < w1) out[q * ld + col[s]] = acc[s];
-  }
-  if (e_ptr) {
-    __syncthreads();   // the window's sums are written before its excluded columns are overwritten
-    for (int64_t f = e_ptr[u] + tid; f < e_ptr[u + 1]; f += EASE_SCORE_THREADS) {
-      const int64_t j = e_idx[f];
-      if (j >= w0 && j < w1) out[q * ld + j] = -__builtin_inf();
-    }
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -299,21 +233,6 @@ extern "C" int hsk_ease_score_rows(const int64_t* users, int64_t n_rows, int64_t
                                    const int32_t* x_indices, const double* B, int64_t n_items, int64_t ldb,
                                    int64_t window, const int64_t* excl_indptr, const int32_t* excl_indices, double* out,
                                    int64_t ld, int32_t* status, hsk_stream_t stream) {
-  HSK_REQUIRE(users && x_indptr && x_indices && B && out && status, HSK_ERR_INVALID, "hsk_ease_score_rows: null pointer");
-  HSK_REQUIRE((excl_indptr == nullptr) == (excl_indices == nullptr), HSK_ERR_INVALID,
-              "hsk_ease_score_rows: exclude CSR needs both arrays");
-  HSK_REQUIRE(n_rows > 0 && n_users > 0 && n_items > 0 && n_items < INT_MAX && ldb >= n_items && ld >= n_items,
-              HSK_ERR_INVALID, "hsk_ease_score_rows: bad shape");
-  HSK_REQUIRE(window >= 1, HSK_ERR_INVALID, "hsk_ease_score_rows: window %lld < 1", (long long)window);
-  const int64_t wlen = window < n_items ? window : n_items;
-  const int64_t nw = hsk_ceil_div(n_items, wlen);
-  HSK_REQUIRE(nw < (1ll << 31), HSK_ERR_INVALID, "hsk_ease_score_rows: too many windows");
-  for (int64_t at = 0; at < n_rows; at += 65535) {   // grid.y limit
-    const int64_t part = n_rows - at < 65535 ? n_rows - at : 65535;
-    k_ease_score<<<dim3((unsigned)nw, (unsigned)part), EASE_SCORE_THREADS, 0, (hipStream_t)stream>>>(
-        users + at, n_users, x_indptr, x_indices, B, n_items, ldb, wlen, excl_indptr, excl_indices, out + at * ld, ld,
-        status);
-    HSK_LAUNCH_CHECK();
-  }
-  return HSK_OK;
+  return hsk_gather_score_rows<false>("hsk_ease_score_rows", users, n_rows, n_users, x_indptr, x_indices, B, n_items, ldb,
+                                      nullptr, 1.0, window, excl_indptr, excl_indices, out, ld, status, stream);
 }

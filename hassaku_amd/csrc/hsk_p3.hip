@@ -3,26 +3,22 @@
 // with the element-wise power.  DESIGN.md section 5.3.
 //
 // Gram geometry: a workgroup of four waves owns 128 x 128 outputs, wave (wm, wn) the 64 x 64 block at (64 wm, 64 wn) in
-// 4 x 4 accumulator tiles of 16 x 16 (operand and C/D maps as in k_ease_update).  The k loop walks k_pad in blocks of
+// 4 x 4 accumulator tiles of 16 x 16 (the tile loop and its operand and C/D maps: hsk_f64_tile.h).  The k loop walks k_pad in blocks of
 // P3_BK = 64 users.  Both operands are rows of the same item-major int8 matrix M; a block's two [128 items][64 B] tiles
 // are loaded 16 bytes per lane (as knn_gload does) one block ahead of the MFMAs, and are converted to fp64 once, when
 // they are written to LDS as k-major [64][128 + 16 pad] images -- the B side multiplied by col_weight there, which is
 // exact (the product is 0 or w_u).  Row tile and column tile walk k in the same order and every product is w_u or 0 on
 // both sides of the diagonal, so the unscaled result is bitwise symmetric.
-#include "hsk_common.h"
+#include "hsk_f64_tile.h"
+#include "hsk_gather_score.h"
 
 #include <limits.h>
-#include <math.h>
 
 #define P3_TILE 128
 #define P3_BK 64
 #define P3_LDS_ROW 144                          // 128 doubles + 16 pad: rows k and k + 1 start 32 banks apart
 #define P3_IMAGE (P3_BK * P3_LDS_ROW)           // doubles of one operand image: 73 728 bytes, two of them 147 456
-#define P3_SCORE_THREADS 256
-#define P3_SCORE_PER 4                          // columns per thread and pass of the scorer
 
-typedef double hsk_p_f64x4 __attribute__((ext_vector_type(4)));
-typedef double hsk_p_f64x2 __attribute__((ext_vector_type(2)));
 typedef int hsk_p_i32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
@@ -41,7 +37,7 @@ __global__ void __launch_bounds__(256) k_p3_inv_degrees(const int64_t* __restric
 // ---------------------------------------------------------------------------------------------
 struct p3_stage {
   hsk_p_i32x4 a[2], b[2];
-  hsk_p_f64x2 w[8];   // col_weight of this lane's 16 k of the block
+  hsk_f64x2 w[8];   // col_weight of this lane's 16 k of the block
 };
 
 __device__ __forceinline__ void p3_gload(p3_stage& s, const int8_t* __restrict__ M, const double* __restrict__ cw,
@@ -54,7 +50,7 @@ __device__ __forceinline__ void p3_gload(p3_stage& s, const int8_t* __restrict__
     s.b[q] = *reinterpret_cast<const hsk_p_i32x4*>(M + (n0 + row) * k_pad + k0);
   }
 #pragma unroll
-  for (int t = 0; t < 8; ++t) s.w[t] = *reinterpret_cast<const hsk_p_f64x2*>(cw + k0 + 2 * t);
+  for (int t = 0; t < 8; ++t) s.w[t] = *reinterpret_cast<const hsk_f64x2*>(cw + k0 + 2 * t);
 }
 
 // int8 -> fp64 once, on the way into the k-major images: sa[k][item] = M[m0 + item, k], sb[k][item] = w_k M[n0 + item, k]
@@ -82,17 +78,12 @@ __global__ void __launch_bounds__(256) k_p3_gram(const int8_t* __restrict__ M, i
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* sa = lds;              // rows m0 .. m0 + 128 of M, k-major
   double* sb = lds + P3_IMAGE;   // rows n0 .. n0 + 128 of M times col_weight, k-major
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
   const int64_t m0 = r0 + (int64_t)blockIdx.y * P3_TILE, n0 = (int64_t)blockIdx.x * P3_TILE;
   const int NK = (int)(k_pad / P3_BK);
-  hsk_p_f64x4 acc[4][4];
-#pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int nj = 0; nj < 4; ++nj)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) acc[mi][nj][v] = 0.0;
+  hsk_f64x4 acc[4][4];
+  hsk_f64_tile_zero(acc);
   p3_stage s;
   p3_gload(s, M, col_weight, k_pad, m0, n0, 0, tid);
   p3_sstore(s, sa, sb, tid);
@@ -100,94 +91,21 @@ __global__ void __launch_bounds__(256) k_p3_gram(const int8_t* __restrict__ M, i
   for (int kt = 0; kt < NK; ++kt) {
     const bool more = kt + 1 < NK;
     if (more) p3_gload(s, M, col_weight, k_pad, m0, n0, kt + 1, tid);   // in flight under this block's MFMAs
-    // A operand: lane holds A[row = lane & 15][k = lane >> 4]; B operand: B[k = lane >> 4][col = lane & 15]
-#pragma unroll 4
-    for (int ks = 0; ks < P3_BK / 4; ++ks) {
-      double af[4], bf[4];
-      const int k = ks * 4 + lq;
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi) af[mi] = sa[k * P3_LDS_ROW + wm * 64 + mi * 16 + lc];
-#pragma unroll
-      for (int nj = 0; nj < 4; ++nj) bf[nj] = sb[k * P3_LDS_ROW + wn * 64 + nj * 16 + lc];
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 4; ++nj)
-          acc[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[mi], bf[nj], acc[mi][nj], 0, 0, 0);
-    }
+    hsk_f64_tile_mma<4, P3_BK, P3_LDS_ROW, 4, false>(acc, sa, wm * 64, sb, wn * 64, lane);
     __syncthreads();   // every wave has read this block's images
     if (more) {
       p3_sstore(s, sa, sb, tid);
       __syncthreads();
     }
   }
-  // f64 16x16x4 C/D map: column = lane & 15, row = (lane >> 4) + 4 v
+  auto store_row = [&](int64_t gi, const int64_t(&gj)[4], const double(&x)[4]) {
+    if (gi >= r1) return;
+    const double sc = row_scale ? row_scale[gi] : 1.0;
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int64_t gi = m0 + wm * 64 + mi * 16 + lq + 4 * v;
-      if (gi >= r1) continue;
-      const double sc = row_scale ? row_scale[gi] : 1.0;
-#pragma unroll
-      for (int nj = 0; nj < 4; ++nj) {
-        const int64_t gj = n0 + wn * 64 + nj * 16 + lc;
-        if (gj < n) out[gi * ld + gj] = row_scale ? sc * acc[mi][nj][v] : acc[mi][nj][v];
-      }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// scoring: out[q, j] = pow(inv_deg_u[u] * (((0 + W[i1, j]) + W[i2, j]) + ...), alpha) over the items of user
-// u = users[q] in stored (ascending) order; loop, windows, exclusion and status as in k_ease_score
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(P3_SCORE_THREADS) k_p3_score(
-    const int64_t* __restrict__ users, int64_t n_users, const int64_t* __restrict__ x_ptr,
-    const int32_t* __restrict__ x_idx, const double* __restrict__ W, int64_t n_items, int64_t ldw,
-    const double* __restrict__ inv_deg_u, double alpha, int64_t window, const int64_t* __restrict__ e_ptr,
-    const int32_t* __restrict__ e_idx, double* __restrict__ out, int64_t ld, int32_t* __restrict__ status) {
-#pragma clang fp contract(off)
-  const int tid = threadIdx.x;
-  const int64_t q = blockIdx.y, w0 = (int64_t)blockIdx.x * window;
-  const int64_t w1 = w0 + window < n_items ? w0 + window : n_items;
-  int64_t u = users[q];
-  if (u < 0 || u >= n_users) {
-    if (tid == 0) atomicOr(status, HSK_STATUS_BAD_INDEX);
-    u = 0;
-  }
-  const int64_t lo = x_ptr[u], hi = x_ptr[u + 1];
-  const double wu = inv_deg_u[u];
-  const bool plain = alpha == 1.0;
-  for (int64_t c0 = w0; c0 < w1; c0 += P3_SCORE_THREADS * P3_SCORE_PER) {
-    double acc[P3_SCORE_PER];
-    int64_t col[P3_SCORE_PER];
-#pragma unroll
-    for (int s = 0; s < P3_SCORE_PER; ++s) {
-      acc[s] = 0.0;
-      col[s] = c0 + s * P3_SCORE_THREADS + tid;
-    }
-    for (int64_t e = lo; e < hi; ++e) {
-      const int32_t i = x_idx[e];
-      if (i < 0 || i >= n_items) continue;
-      const double* row = W + (int64_t)i * ldw;
-#pragma unroll
-      for (int s = 0; s < P3_SCORE_PER; ++s)
-        if (col[s] < w1) acc[s] = acc[s] + row[col[s]];
-    }
-#pragma unroll
-    for (int s = 0; s < P3_SCORE_PER; ++s)
-      if (col[s] < w1) {
-        const double p = wu * acc[s];
-        out[q * ld + col[s]] = plain ? p : (p == 0.0 ? 0.0 : pow(p, alpha));   // a zero sum gives +0.0
-      }
-  }
-  if (e_ptr) {
-    __syncthreads();   // the window's scores are written before its excluded columns are overwritten
-    for (int64_t f = e_ptr[u] + tid; f < e_ptr[u + 1]; f += P3_SCORE_THREADS) {
-      const int64_t j = e_idx[f];
-      if (j >= w0 && j < w1) out[q * ld + j] = -__builtin_inf();
-    }
-  }
+    for (int nj = 0; nj < 4; ++nj)
+      if (gj[nj] < n) out[gi * ld + gj[nj]] = row_scale ? sc * x[nj] : x[nj];
+  };
+  hsk_f64_tile_rows(acc, m0 + wm * 64, n0 + wn * 64, lane, store_row);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -231,24 +149,6 @@ extern "C" int hsk_p3_score_rows(const int64_t* users, int64_t n_rows, int64_t n
                                  const double* inv_deg_u, double alpha, int64_t window, const int64_t* excl_indptr,
                                  const int32_t* excl_indices, double* out, int64_t ld, int32_t* status,
                                  hsk_stream_t stream) {
-  HSK_REQUIRE(users && x_indptr && x_indices && W && inv_deg_u && out && status, HSK_ERR_INVALID,
-              "hsk_p3_score_rows: null pointer");
-  HSK_REQUIRE((excl_indptr == nullptr) == (excl_indices == nullptr), HSK_ERR_INVALID,
-              "hsk_p3_score_rows: exclude CSR needs both arrays");
-  HSK_REQUIRE(n_rows > 0 && n_users > 0 && n_items > 0 && n_items < INT_MAX && ldw >= n_items && ld >= n_items,
-              HSK_ERR_INVALID, "hsk_p3_score_rows: bad shape");
-  HSK_REQUIRE(alpha > 0.0 && alpha < __builtin_inf(), HSK_ERR_INVALID, "hsk_p3_score_rows: alpha %g is not in (0, inf)",
-              alpha);
-  HSK_REQUIRE(window >= 1, HSK_ERR_INVALID, "hsk_p3_score_rows: window %lld < 1", (long long)window);
-  const int64_t wlen = window < n_items ? window : n_items;
-  const int64_t nw = hsk_ceil_div(n_items, wlen);
-  HSK_REQUIRE(nw < (1ll << 31), HSK_ERR_INVALID, "hsk_p3_score_rows: too many windows");
-  for (int64_t at = 0; at < n_rows; at += 65535) {   // grid.y limit
-    const int64_t part = n_rows - at < 65535 ? n_rows - at : 65535;
-    k_p3_score<<<dim3((unsigned)nw, (unsigned)part), P3_SCORE_THREADS, 0, (hipStream_t)stream>>>(
-        users + at, n_users, x_indptr, x_indices, W, n_items, ldw, inv_deg_u, alpha, wlen, excl_indptr, excl_indices,
-        out + at * ld, ld, status);
-    HSK_LAUNCH_CHECK();
-  }
-  return HSK_OK;
+  return hsk_gather_score_rows<true>("hsk_p3_score_rows", users, n_rows, n_users, x_indptr, x_indices, W, n_items, ldw,
+                                     inv_deg_u, alpha, window, excl_indptr, excl_indices, out, ld, status, stream);
 }

@@ -11,8 +11,9 @@
 // and k + 1 start 32 banks apart); an operand stored inner-dimension-major in global memory (the rows of A in A^T B,
 // the rows of Q) is copied, one stored the other way (the rows of A in A Q, the factor rows of the scorer) is
 // transposed on the way in.  Everything outside the operands reads as 0.0, so any 1 <= b <= HSK_SVD_MAX_BLOCK works.
-// The next block's global loads are in flight under this block's MFMAs.
-#include "hsk_common.h"
+// The next block's global loads are in flight under this block's MFMAs.  The tile loop and its operand and C/D maps
+// are hsk_f64_tile.h's.
+#include "hsk_f64_tile.h"
 
 #include <limits.h>
 
@@ -23,9 +24,6 @@
 #define SVD_SPMM_DEPTH 8                    // gathered rows in flight per wave
 #define SVD_RES_COLS 16                     // columns per workgroup of the residual kernel
 #define SVD_GRAM_TARGET_WGS 1024            // the Gram's grid: tiles x row splits is about this many workgroups
-
-typedef double hsk_s_f64x4 __attribute__((ext_vector_type(4)));
-typedef double hsk_s_f64x2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------
 // sparse x dense: one wave per (CSR row, 128 columns), lane = one pair of columns
@@ -43,9 +41,9 @@ __global__ void __launch_bounds__(256) k_svd_spmm(const int64_t* __restrict__ in
   if (c >= b) return;
   const int64_t lo = indptr[r], hi = indptr[r + 1];
   const double* __restrict__ col = V + c;
-  hsk_s_f64x2 acc = {0.0, 0.0};
+  hsk_f64x2 acc = {0.0, 0.0};
   for (int64_t e = lo; e < hi; e += SVD_SPMM_DEPTH) {
-    hsk_s_f64x2 x[SVD_SPMM_DEPTH];
+    hsk_f64x2 x[SVD_SPMM_DEPTH];
     bool ok[SVD_SPMM_DEPTH];
 #pragma unroll
     for (int t = 0; t < SVD_SPMM_DEPTH; ++t) {
@@ -53,7 +51,7 @@ __global__ void __launch_bounds__(256) k_svd_spmm(const int64_t* __restrict__ in
       ok[t] = i >= 0 && i < n_cols;
       // c and ldv are even: the pair (c, c + 1) is inside its row even where c + 1 == b.  A slot past the row's end
       // (or a bad id) loads row 0 and is not added, so the loads carry no branch and all of them are in flight.
-      x[t] = *reinterpret_cast<const hsk_s_f64x2*>(col + (int64_t)(ok[t] ? i : 0) * ldv);
+      x[t] = *reinterpret_cast<const hsk_f64x2*>(col + (int64_t)(ok[t] ? i : 0) * ldv);
     }
 #pragma unroll
     for (int t = 0; t < SVD_SPMM_DEPTH; ++t)
@@ -61,7 +59,7 @@ __global__ void __launch_bounds__(256) k_svd_spmm(const int64_t* __restrict__ in
   }
   double* o = out + r * ldo + c;
   if (c + 1 < b) {
-    *reinterpret_cast<hsk_s_f64x2*>(o) = acc;
+    *reinterpret_cast<hsk_f64x2*>(o) = acc;
   } else {
     *o = acc[0];
   }
@@ -71,7 +69,7 @@ __global__ void __launch_bounds__(256) k_svd_spmm(const int64_t* __restrict__ in
 // the tile kernel
 // ---------------------------------------------------------------------------------------------
 struct svd_stage {
-  hsk_s_f64x2 v[4];
+  hsk_f64x2 v[4];
 };
 
 // source stored inner-dimension-major: P[k, c], k in [k0, k1), c in [c0, C)
@@ -81,9 +79,9 @@ __device__ __forceinline__ void svd_gload_k(svd_stage& s, const double* __restri
   for (int q = 0; q < 4; ++q) {
     const int t = tid + 256 * q;
     const int64_t k = k0 + (t >> 5), c = c0 + (t & 31) * 2;
-    hsk_s_f64x2 x = {0.0, 0.0};
+    hsk_f64x2 x = {0.0, 0.0};
     if (k < k1 && c < C) {
-      x = *reinterpret_cast<const hsk_s_f64x2*>(P + k * ld + c);
+      x = *reinterpret_cast<const hsk_f64x2*>(P + k * ld + c);
       if (c + 1 >= C) x[1] = 0.0;
     }
     s.v[q] = x;
@@ -94,7 +92,7 @@ __device__ __forceinline__ void svd_sstore_k(const svd_stage& s, double* __restr
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int t = tid + 256 * q;
-    *reinterpret_cast<hsk_s_f64x2*>(img + (t >> 5) * SVD_LDS_ROW + (t & 31) * 2) = s.v[q];
+    *reinterpret_cast<hsk_f64x2*>(img + (t >> 5) * SVD_LDS_ROW + (t & 31) * 2) = s.v[q];
   }
 }
 
@@ -106,7 +104,7 @@ __device__ __forceinline__ void svd_gload_c(svd_stage& s, const double* __restri
   for (int q = 0; q < 4; ++q) {
     const int t = tid + 256 * q;
     const int64_t c = c0 + (t >> 4), k = k0 + (t & 15) * 2;
-    hsk_s_f64x2 x = {0.0, 0.0};
+    hsk_f64x2 x = {0.0, 0.0};
     if (c < C && k < k1) {
       int64_t row = c;
       if (rows) {
@@ -116,7 +114,7 @@ __device__ __forceinline__ void svd_gload_c(svd_stage& s, const double* __restri
           row = 0;
         }
       }
-      x = *reinterpret_cast<const hsk_s_f64x2*>(P + row * ld + k);
+      x = *reinterpret_cast<const hsk_f64x2*>(P + row * ld + k);
       if (k + 1 >= k1) x[1] = 0.0;
     }
     s.v[q] = x;
@@ -143,17 +141,12 @@ __global__ void __launch_bounds__(256) k_svd_tile(const double* __restrict__ A, 
                                                   int64_t out_stride, int32_t* __restrict__ status) {
   __shared__ __attribute__((aligned(16))) double sa[SVD_IMAGE];
   __shared__ __attribute__((aligned(16))) double sb[SVD_IMAGE];
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave >> 1, wn = wave & 1;
   const int64_t m0 = (int64_t)blockIdx.x * SVD_TILE, n0 = (int64_t)blockIdx.y * SVD_TILE;
   const int64_t kb = (int64_t)blockIdx.z * k_per, ke = kb + k_per < K ? kb + k_per : K;
-  hsk_s_f64x4 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int nj = 0; nj < 2; ++nj)
-#pragma unroll
-      for (int v = 0; v < 4; ++v) acc[mi][nj][v] = 0.0;
+  hsk_f64x4 acc[2][2];
+  hsk_f64_tile_zero(acc);
   svd_stage ra, rb;
   auto gload = [&](int64_t k0) {
     if (A_K) svd_gload_k(ra, A, lda, k0, ke, m0, M, tid);
@@ -173,41 +166,21 @@ __global__ void __launch_bounds__(256) k_svd_tile(const double* __restrict__ A, 
   for (int64_t k0 = kb; k0 < ke; k0 += SVD_BK) {
     const bool more = k0 + SVD_BK < ke;
     if (more) gload(k0 + SVD_BK);
-    // A operand: lane holds A[row = lane & 15][k = lane >> 4]; B operand: B[k = lane >> 4][col = lane & 15]
-#pragma unroll
-    for (int ks = 0; ks < SVD_BK / 4; ++ks) {
-      double af[2], bf[2];
-      const int k = ks * 4 + lq;
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi) af[mi] = sa[k * SVD_LDS_ROW + wm * 32 + mi * 16 + lc];
-#pragma unroll
-      for (int nj = 0; nj < 2; ++nj) bf[nj] = sb[k * SVD_LDS_ROW + wn * 32 + nj * 16 + lc];
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int nj = 0; nj < 2; ++nj)
-          acc[mi][nj] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[mi], bf[nj], acc[mi][nj], 0, 0, 0);
-    }
+    hsk_f64_tile_mma<2, SVD_BK, SVD_LDS_ROW, SVD_BK / 4, false>(acc, sa, wm * 32, sb, wn * 32, lane);
     __syncthreads();   // every wave has read this block's images
     if (more) {
       sstore();
       __syncthreads();
     }
   }
-  // f64 16x16x4 C/D map: column = lane & 15, row = (lane >> 4) + 4 v
   double* __restrict__ o = out + (int64_t)blockIdx.z * out_stride;
+  auto store_row = [&](int64_t gi, const int64_t(&gj)[2], const double(&x)[2]) {
+    if (gi >= M) return;
 #pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int64_t gi = m0 + wm * 32 + mi * 16 + lq + 4 * v;
-      if (gi >= M) continue;
-#pragma unroll
-      for (int nj = 0; nj < 2; ++nj) {
-        const int64_t gj = n0 + wn * 32 + nj * 16 + lc;
-        if (gj < N) o[gi * ldo + gj] = acc[mi][nj][v];
-      }
-    }
+    for (int nj = 0; nj < 2; ++nj)
+      if (gj[nj] < N) o[gi * ldo + gj[nj]] = x[nj];
+  };
+  hsk_f64_tile_rows(acc, m0 + wm * 32, n0 + wn * 32, lane, store_row);
 }
 
 // H[i, j] = ((0 + P_0[i, j]) + P_1[i, j]) + ... over the row splits in ascending order
@@ -238,8 +211,8 @@ __global__ void __launch_bounds__(256) k_svd_residuals(const double* __restrict_
     const bool two = c + 1 < b;
     const double t0 = theta[c], t1 = two ? theta[c + 1] : 0.0;
     for (int64_t r = rr; r < n; r += 32) {
-      const hsk_s_f64x2 y = *reinterpret_cast<const hsk_s_f64x2*>(Y + r * ldy + c);
-      const hsk_s_f64x2 v = *reinterpret_cast<const hsk_s_f64x2*>(V + r * ldv + c);
+      const hsk_f64x2 y = *reinterpret_cast<const hsk_f64x2*>(Y + r * ldy + c);
+      const hsk_f64x2 v = *reinterpret_cast<const hsk_f64x2*>(V + r * ldv + c);
       const double d0 = y[0] - t0 * v[0];
       s0 = s0 + d0 * d0;
       if (two) {

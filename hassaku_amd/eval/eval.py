@@ -5,8 +5,8 @@ HIP matrix-factorisation model it does not densify anything on the host: per chu
 hsk_mf_eval_topk (fp32-MFMA scores of the chunk against the item table, -inf on the user's excluded items
 read from the exclude CSR, top-100) and hsk_rank_metrics (precision / recall / ndcg at 5,10,50,100 from
 the ground-truth CSR), then accumulates per-group sums exactly as FullEvaluator does.  A sparse-matrix model
-(ItemKNN / UserKNN) scores chunks of users into float64 rows on the device (hsk_knn_score_rows, excluded items -inf),
-then hsk_knn_topk_rows and hsk_rank_metrics (eval/eval.py:222-236 there: float64 scores, topk(100)).  Any other
+(ItemKNN / UserKNN, EASE, P3alpha, SVD) scores chunks of users into float64 rows on the device (its `score_rows`,
+excluded items -inf), then hsk_knn_topk_rows and hsk_rank_metrics (eval/eval.py:222-236 there: float64 scores, topk(100)).  Any other
 `RecommenderAlgorithm` goes through the generic dense path (predict -> mask -> eval_batch).
 """
 from collections import defaultdict

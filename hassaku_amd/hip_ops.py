@@ -747,6 +747,33 @@ def rank_metrics(topk_idx: torch.Tensor, u_idx: torch.Tensor, label_indptr: torc
 
 
 # ---------------------------------------------------------------------------------------------------
+# shared by the row scorers of the fitted models (knn, ease, p3, svd)
+# ---------------------------------------------------------------------------------------------------
+def _excl_pair(excl):
+    """(indptr, indices) of an exclusion CSR, checked, or (None, None)."""
+    if excl is None:
+        return None, None
+    ep, ei = excl
+    _chk(ep, torch.int64, 'excl_indptr')
+    _chk(ei, torch.int32, 'excl_indices')
+    return ep, ei
+
+
+def _score_out(out: Optional[torch.Tensor], R: int, n_cols: int, device) -> torch.Tensor:
+    """The fp64 score buffer of R rows x n_cols columns: `out` checked, or a new one."""
+    if out is None:
+        out = torch.empty((R, n_cols), dtype=torch.float64, device=device)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_cols:
+        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_cols})')
+    return out
+
+
+def _status_word(status: Optional[torch.Tensor], device) -> torch.Tensor:
+    return torch.zeros(1, dtype=torch.int32, device=device) if status is None else status
+
+
+# ---------------------------------------------------------------------------------------------------
 # ItemKNN / UserKNN (hsk_knn.hip)
 # ---------------------------------------------------------------------------------------------------
 KNN_KINDS = {'cosine': 0, 'jaccard': 1, 'sorensen_dice': 2, 'asymmetric_cosine': 3, 'tversky': 4}
@@ -828,17 +855,8 @@ def knn_score_rows(users: torch.Tensor, a_csr, b_csr, n_cols: int, window: int =
         _chk(p, torch.int64, f'{name}_indptr', (nr + 1,))
         _chk(i, torch.int32, f'{name}_indices')
         _chk(v, torch.float64, f'{name}_vals', (i.numel(),), optional=True)
-    ep, ei = excl if excl is not None else (None, None)
-    if excl is not None:
-        _chk(ep, torch.int64, 'excl_indptr')
-        _chk(ei, torch.int32, 'excl_indices')
-    if out is None:
-        out = torch.empty((R, n_cols), dtype=torch.float64, device=users.device)
-    _chk(out, torch.float64, 'out')
-    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_cols:
-        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_cols})')
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    ep, ei = _excl_pair(excl)
+    out, status = _score_out(out, R, n_cols, users.device), _status_word(status, users.device)
     window = max(1, min(int(window), KNN_MAX_WINDOW))
     _lib.check(lib.hsk_knn_score_rows(_p(users), R, an, _p(ap), _p(ai), _p(av), bn, _p(bp), _p(bi), _p(bv), n_cols,
                                       window, _p(ep), _p(ei), _p(out), out.shape[1], _p(status), _stream()),
@@ -915,10 +933,9 @@ def ease_weights(P: torch.Tensor) -> torch.Tensor:
     return P
 
 
-def ease_score_rows(users: torch.Tensor, x_csr, B: torch.Tensor, window: int = 1024, excl=None,
-                    out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp64 [R, n_items]: row q = sum of the rows of B picked by the items of train row users[q], in stored order.
-    x_csr: (indptr int64, indices int32, n_users); excl: (indptr, indices) -> those columns -inf."""
+def _gather_score_rows(users, x_csr, W, name, scale, window, excl, out, status):
+    """ease_score_rows (scale None) and p3_score_rows (scale = (inv_deg_u, alpha)): hsk_gather_score.h's two entry
+    points."""
     _lib.require_gpu()
     lib = _lib.load()
     _chk(users, torch.int64, 'users')
@@ -926,25 +943,31 @@ def ease_score_rows(users: torch.Tensor, x_csr, B: torch.Tensor, window: int = 1
     xp, xi, n_users = x_csr
     _chk(xp, torch.int64, 'x_indptr', (n_users + 1,))
     _chk(xi, torch.int32, 'x_indices')
-    _chk(B, torch.float64, 'B')
-    if B.dim() != 2 or B.shape[1] < B.shape[0]:
-        raise ValueError(f'B has shape {tuple(B.shape)}, expected [n_items, ld >= n_items]')
-    n_items = B.shape[0]
-    ep, ei = excl if excl is not None else (None, None)
-    if excl is not None:
-        _chk(ep, torch.int64, 'excl_indptr')
-        _chk(ei, torch.int32, 'excl_indices')
-    if out is None:
-        out = torch.empty((R, n_items), dtype=torch.float64, device=users.device)
-    _chk(out, torch.float64, 'out')
-    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_items:
-        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_items})')
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=users.device)
-    _lib.check(lib.hsk_ease_score_rows(_p(users), R, n_users, _p(xp), _p(xi), _p(B), n_items, B.shape[1],
-                                       max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1], _p(status),
-                                       _stream()), 'hsk_ease_score_rows')
+    _chk(W, torch.float64, name)
+    if W.dim() != 2 or W.shape[1] < W.shape[0]:
+        raise ValueError(f'{name} has shape {tuple(W.shape)}, expected [n_items, ld >= n_items]')
+    n_items = W.shape[0]
+    if scale is not None:
+        inv_deg_u, alpha = scale
+        if inv_deg_u.numel() < n_users:
+            raise ValueError(f'inv_deg_u has {inv_deg_u.numel()} entries, needs {n_users}')
+        _chk(inv_deg_u, torch.float64, 'inv_deg_u')
+    ep, ei = _excl_pair(excl)
+    out, status = _score_out(out, R, n_items, users.device), _status_word(status, users.device)
+    head = (_p(users), R, n_users, _p(xp), _p(xi), _p(W), n_items, W.shape[1])
+    tail = (max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1], _p(status), _stream())
+    if scale is None:
+        _lib.check(lib.hsk_ease_score_rows(*head, *tail), 'hsk_ease_score_rows')
+    else:
+        _lib.check(lib.hsk_p3_score_rows(*head, _p(inv_deg_u), float(alpha), *tail), 'hsk_p3_score_rows')
     return out
+
+
+def ease_score_rows(users: torch.Tensor, x_csr, B: torch.Tensor, window: int = 1024, excl=None,
+                    out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [R, n_items]: row q = sum of the rows of B picked by the items of train row users[q], in stored order.
+    x_csr: (indptr int64, indices int32, n_users); excl: (indptr, indices) -> those columns -inf."""
+    return _gather_score_rows(users, x_csr, B, 'B', None, window, excl, out, status)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -987,35 +1010,7 @@ def p3_score_rows(users: torch.Tensor, x_csr, W: torch.Tensor, inv_deg_u: torch.
     """fp64 [R, n_items]: row q = (inv_deg_u[u] * sum of the rows of W picked by the items of train row u = users[q],
     in stored order) ** alpha.  x_csr: (indptr int64, indices int32, n_users); excl: (indptr, indices) -> those
     columns -inf."""
-    _lib.require_gpu()
-    lib = _lib.load()
-    _chk(users, torch.int64, 'users')
-    R = users.numel()
-    xp, xi, n_users = x_csr
-    _chk(xp, torch.int64, 'x_indptr', (n_users + 1,))
-    _chk(xi, torch.int32, 'x_indices')
-    _chk(W, torch.float64, 'W')
-    if W.dim() != 2 or W.shape[1] < W.shape[0]:
-        raise ValueError(f'W has shape {tuple(W.shape)}, expected [n_items, ld >= n_items]')
-    n_items = W.shape[0]
-    if inv_deg_u.numel() < n_users:
-        raise ValueError(f'inv_deg_u has {inv_deg_u.numel()} entries, needs {n_users}')
-    _chk(inv_deg_u, torch.float64, 'inv_deg_u')
-    ep, ei = excl if excl is not None else (None, None)
-    if excl is not None:
-        _chk(ep, torch.int64, 'excl_indptr')
-        _chk(ei, torch.int32, 'excl_indices')
-    if out is None:
-        out = torch.empty((R, n_items), dtype=torch.float64, device=users.device)
-    _chk(out, torch.float64, 'out')
-    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_items:
-        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_items})')
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=users.device)
-    _lib.check(lib.hsk_p3_score_rows(_p(users), R, n_users, _p(xp), _p(xi), _p(W), n_items, W.shape[1], _p(inv_deg_u),
-                                     float(alpha), max(1, int(window)), _p(ep), _p(ei), _p(out), out.shape[1],
-                                     _p(status), _stream()), 'hsk_p3_score_rows')
-    return out
+    return _gather_score_rows(users, x_csr, W, 'W', (inv_deg_u, alpha), window, excl, out, status)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1149,17 +1144,8 @@ def svd_score_rows(users: torch.Tensor, UF: torch.Tensor, IF: torch.Tensor, excl
     n_items, ki, ldi = _svd_dense(IF, 'IF')
     if ki != k:
         raise ValueError(f'UF {tuple(UF.shape)} and IF {tuple(IF.shape)} differ in the number of factors')
-    ep, ei = excl if excl is not None else (None, None)
-    if excl is not None:
-        _chk(ep, torch.int64, 'excl_indptr')
-        _chk(ei, torch.int32, 'excl_indices')
-    if out is None:
-        out = torch.empty((R, n_items), dtype=torch.float64, device=users.device)
-    _chk(out, torch.float64, 'out')
-    if out.dim() != 2 or out.shape[0] < R or out.shape[1] < n_items:
-        raise ValueError(f'out has shape {tuple(out.shape)}, needs at least ({R}, {n_items})')
-    if status is None:
-        status = torch.zeros(1, dtype=torch.int32, device=users.device)
+    ep, ei = _excl_pair(excl)
+    out, status = _score_out(out, R, n_items, users.device), _status_word(status, users.device)
     _lib.check(lib.hsk_svd_score_rows(_p(users), R, n_users, _p(UF), ldu, _p(IF), ldi, n_items, k, _p(ep), _p(ei),
                                       _p(out), out.shape[1], _p(status), _stream()), 'hsk_svd_score_rows')
     return out

@@ -363,6 +363,28 @@ def test_scores_bitwise_given_weights(name, lam):
 
 
 @pytest.mark.gpu
+def test_scores_beyond_one_grid_of_rows():
+    """65 535 + 3 user ids in one call (the launcher splits the rows at the grid's 65 535): every row is bitwise the
+    row a 5-row call gives for that user.  5 users, one without items, 70 items in three windows of 32 (the last
+    partial) and an exclusion CSR."""
+    import torch
+    from hassaku_amd.data.csr import UserItemCsr
+    rng = np.random.RandomState(11)
+    ur, uc = np.nonzero(rng.rand(5, 70) < 0.3)
+    train = UserItemCsr.from_pairs(ur[ur != 3], uc[ur != 3], 5, 70)
+    er_, ec_ = np.nonzero(rng.rand(5, 70) < 0.2)
+    ep, ei = UserItemCsr.from_pairs(er_, ec_, 5, 70).to_device('cuda')
+    m = _model_with(train, rng.standard_normal((70, 70)))
+    m.WINDOW = 32
+    ids = torch.arange(65535 + 3, device='cuda') % 5
+    few = m.score_rows(torch.arange(5, device='cuda'), excl=(ep, ei))
+    assert torch.isinf(few).any() and bool((few[3][~torch.isinf(few[3])] == 0).all())
+    many = m.score_rows(ids, excl=(ep, ei))
+    assert many.shape == (65535 + 3, 70) and torch.equal(many, few[ids])
+    m.check_indices()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('name, lam', CASES + [('g11', 50.7)])
 def test_fit_scores_ranking_metrics(name, lam):
     """After fit: |S_gpu - S_ref| <= tol (|X||B_ref|) element by element, tol = 8 x the same quantity between the

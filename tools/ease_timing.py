@@ -20,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hassaku_amd import hip_ops  # noqa: E402
-from hassaku_amd.algorithms.knn_algs import _transpose  # noqa: E402
+from hassaku_amd.algorithms.base_classes import csr_transpose  # noqa: E402
 from hassaku_amd.algorithms.linear_algs import EASE  # noqa: E402
 from hassaku_amd.data.csr import UserItemCsr  # noqa: E402
 from hassaku_amd.data.synthetic import generate_named  # noqa: E402
@@ -37,7 +37,7 @@ def time_fit(model, train):
     n_users, n = train.n_rows, train.n_cols
     x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
     t0 = _now()
-    t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n)
+    t_ptr, t_idx, _ = csr_transpose(x_ptr, x_idx, None, n_users, n)
     M = hip_ops.knn_pack_i8(t_ptr, t_idx, n, n_users)
     t1 = _now()
     block = model._gram_block(n)

@@ -19,7 +19,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hassaku_amd import hip_ops  # noqa: E402
-from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN, _transpose  # noqa: E402
+from hassaku_amd.algorithms.base_classes import csr_transpose  # noqa: E402
+from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN  # noqa: E402
 from hassaku_amd.data.csr import UserItemCsr  # noqa: E402
 from hassaku_amd.data.synthetic import generate_named  # noqa: E402
 
@@ -38,7 +39,7 @@ def time_fit(model, train):
     x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
     t0 = _now()
     if model.ITEM_BASED:
-        e_ptr, e_idx, _ = _transpose(x_ptr, x_idx, None, train.n_rows, train.n_cols)
+        e_ptr, e_idx, _ = csr_transpose(x_ptr, x_idx, None, train.n_rows, train.n_cols)
         n_ent, n_feat = train.n_cols, train.n_rows
     else:
         e_ptr, e_idx, n_ent, n_feat = x_ptr, x_idx, train.n_rows, train.n_cols

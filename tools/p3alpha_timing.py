@@ -40,7 +40,7 @@ def worker(opts):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from hassaku_amd import hip_ops
     from hassaku_amd.algorithms.graph_algs import P3alpha
-    from hassaku_amd.algorithms.knn_algs import _transpose
+    from hassaku_amd.algorithms.base_classes import csr_transpose
     from hassaku_amd.data.csr import UserItemCsr
     from hassaku_amd.data.synthetic import generate_named
 
@@ -86,7 +86,7 @@ def worker(opts):
     # the steps of fit, one by one
     x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
     t0 = now()
-    t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n)
+    t_ptr, t_idx, _ = csr_transpose(x_ptr, x_idx, None, n_users, n)
     M = hip_ops.knn_pack_i8(t_ptr, t_idx, n, n_users)
     t1 = now()
     w_u = hip_ops.p3_inv_degrees(x_ptr, M.shape[1])

@@ -38,7 +38,7 @@ def worker(opts):
 
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from hassaku_amd import hip_ops
-    from hassaku_amd.algorithms.knn_algs import _transpose
+    from hassaku_amd.algorithms.base_classes import csr_transpose
     from hassaku_amd.algorithms.mf_algs import SVDAlgorithm
     from hassaku_amd.data.csr import UserItemCsr
     from hassaku_amd.data.synthetic import generate_named
@@ -90,7 +90,7 @@ def worker(opts):
 
     # the kernels of one iteration, each on its own
     x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
-    t_ptr, t_idx, _ = _transpose(x_ptr, x_idx, None, n_users, n)
+    t_ptr, t_idx, _ = csr_transpose(x_ptr, x_idx, None, n_users, n)
     X, Xt = (x_ptr, x_idx, n), (t_ptr, t_idx, n_users)
     gen = torch.Generator(device=dev).manual_seed(0)
     V, Y, Z = hip_ops.svd_empty(n, b, dev), hip_ops.svd_empty(n, b, dev), hip_ops.svd_empty(n_users, b, dev)
