@@ -79,6 +79,13 @@ SIGNATURES = {
     'hsk_embedding_backward_ws_bytes': (c_int64, [c_int64, c_int64]),
     'hsk_embedding_backward': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
                                        c_void_p, c_void_p]),
+    'hsk_sparse_rows_sum': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                    c_void_p, c_void_p, c_void_p]),
+    'hsk_sparse_rows_offsets': (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    'hsk_sparse_rows_sum_backward_ws_bytes': (c_int64, [c_int64, c_int64]),
+    'hsk_sparse_rows_sum_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                             c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                             c_void_p]),
     'hsk_adamw_dense': (c_int, [c_void_p] * 4 + [c_int64] + [c_double] * 5 + [c_int64, c_void_p]),
     'hsk_opt_dense': (c_int, [c_int] + [c_void_p] * 4 + [c_int64] + [c_double] * 5 + [c_int64, c_void_p]),
     'hsk_sample_negatives_uniform': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,

@@ -1,16 +1,18 @@
 """Name -> class registry (algorithms/algorithms_utils.py:12-30).  Filled: the slot on the hot path (mf), its
 bias-only sibling (sgdbias), the anchor / prototype models that share the embedding gather and the
 neighbourhood models (uknn, iknn), the linear model (ease), the graph model (p3alpha) and the truncated SVD (svd); the
-reference's other algorithms are out of scope.
+reference's other algorithms are out of scope, except its neural model (dmf), which trains
+like the other SGD models but on a sparse first layer.
 
-The registry has five families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
+The registry has six families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
 always has.  `SparseAlgorithmsEnum` holds the neighbourhood models, `LinearAlgorithmsEnum` the linear one and
 `GraphAlgorithmsEnum` the random-walk one and `FactorAlgorithmsEnum` the one-shot factorisation (all fitted once on
 the train CSR).  Every family is reachable by name through `AlgorithmsEnum` (`AlgorithmsEnum['iknn']`,
 `AlgorithmsEnum.ease`, `AlgorithmsEnum.p3alpha`, `AlgorithmsEnum.svd`), so every caller
 that resolves a slot by name -- run_experiment.py, the experiment helpers -- takes any of them.  `ALGORITHM_NAMES` lists the first two families, `ALL_ALGORITHM_NAMES` the first three and
-`REGISTERED_ALGORITHM_NAMES` the first four and `CLI_ALGORITHM_NAMES` all five (the earlier tuples keep their
-contents).  Callers use only a slot's `.name` and `.value`.
+`REGISTERED_ALGORITHM_NAMES` the first four and `CLI_ALGORITHM_NAMES` the first five (the earlier tuples keep their
+contents).  `NeuralAlgorithmsEnum` holds `dmf`, trained by the Trainer like the first family;
+`EXPERIMENT_ALGORITHM_NAMES` = `CLI_ALGORITHM_NAMES` + ('dmf',) is what run_experiment.py offers.  Callers use only a slot's `.name` and `.value`.
 """
 from enum import Enum, EnumMeta
 
@@ -18,6 +20,7 @@ from hassaku_amd.algorithms.graph_algs import P3alpha
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN
 from hassaku_amd.algorithms.linear_algs import EASE
 from hassaku_amd.algorithms.mf_algs import SVDAlgorithm
+from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
 from hassaku_amd.algorithms.proto_alg import ACF, IProtoMF, UIProtoMF, UProtoMF
 from hassaku_amd.algorithms.sgd_alg import SGDBaseline, SGDMatrixFactorization
 
@@ -39,12 +42,17 @@ class FactorAlgorithmsEnum(Enum):
     svd = SVDAlgorithm
 
 
-_OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum, GraphAlgorithmsEnum, FactorAlgorithmsEnum)
+class NeuralAlgorithmsEnum(Enum):
+    dmf = DeepMatrixFactorization
+
+
+_OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum, GraphAlgorithmsEnum, FactorAlgorithmsEnum,
+                   NeuralAlgorithmsEnum)
 
 
 class _RegistryMeta(EnumMeta):
-    """Looks a name up among the SGD slots first, then among the sparse-matrix, the linear, the graph and the factor
-    slots."""
+    """Looks a name up among the SGD slots first, then among the sparse-matrix, the linear, the graph, the factor and
+    the neural slots."""
 
     def __getitem__(cls, name):
         if name in cls._member_map_:
@@ -77,3 +85,4 @@ ALGORITHM_NAMES = tuple(m.name for m in AlgorithmsEnum) + tuple(m.name for m in 
 ALL_ALGORITHM_NAMES = ALGORITHM_NAMES + tuple(m.name for m in LinearAlgorithmsEnum)
 REGISTERED_ALGORITHM_NAMES = ALL_ALGORITHM_NAMES + tuple(m.name for m in GraphAlgorithmsEnum)
 CLI_ALGORITHM_NAMES = REGISTERED_ALGORITHM_NAMES + tuple(m.name for m in FactorAlgorithmsEnum)
+EXPERIMENT_ALGORITHM_NAMES = CLI_ALGORITHM_NAMES + tuple(m.name for m in NeuralAlgorithmsEnum)

@@ -45,6 +45,13 @@ def _fill(target: dict, defaults, added: list):
             added.append(f'{key}={value}')
 
 
+def validate_dmf_conf(conf: dict):
+    """The DeepMatrixFactorization keys of a conf: `u_mid_layers`, `i_mid_layers` (a positive int or a list of them)
+    and `final_dimension` (a positive int), all required; anything else raises ValueError."""
+    from hassaku_amd.algorithms.neural_algs import validate_dmf_conf as check
+    check(conf)
+
+
 def parse_conf(conf: dict, alg, dataset) -> dict:
     """alg / dataset are members of AlgorithmsEnum / DatasetsEnum (only .name and alg.value are used)."""
     from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm
@@ -52,6 +59,7 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
     from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
     from hassaku_amd.algorithms.mf_algs import SVDAlgorithm, validate_svd_conf
+    from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
     from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 
     assert 'data_path' in conf, 'Data path is missing from the configuration file'
@@ -64,6 +72,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
         validate_p3alpha_conf(conf)
     elif issubclass(alg.value, SVDAlgorithm):
         validate_svd_conf(conf)
+    elif issubclass(alg.value, DeepMatrixFactorization):
+        validate_dmf_conf(conf)   # its own keys; the SGD defaults below apply as for any trained model
     conf['alg'] = alg.name
     conf['time_run'] = generate_id()
     conf['dataset'] = dataset.name

@@ -1960,6 +1960,7 @@ extern "C" int hsk_sample_negatives_uniform(const int64_t* csr_indptr, const int
 
 // multi-GPU phases (item table range-sharded, user table row-sharded)
 #include <algorithm>
+#include "hsk_keysort.h"
 #include "hsk_shard.inc"
 #include "hsk_rccl.inc"
 
@@ -2036,15 +2037,12 @@ extern "C" int hsk_embedding_gather(const float* table, int64_t n_rows, int64_t 
   return HSK_OK;
 }
 
-struct hsk_embw {   // scratch of hsk_embedding_backward
-  int* it32;
-  int2* perm1;
-  int *perm, *hist, *btot, *bstart, *offsets;
-  int64_t total;
-};
+bool hsk_keysort_supported(int64_t n_keys, int64_t n) {
+  return n_keys > 0 && n > 0 && n < 0x7fffffff && hsk_sort_hist_elems(n_keys, n) >= 0;
+}
 
-static hsk_embw hsk_embw_carve(void* base, int64_t n_rows, int64_t n) {
-  hsk_embw w;
+hsk_keysort hsk_keysort_carve(void* base, int64_t n_rows, int64_t n) {
+  hsk_keysort w;
   char* p = (char*)base;
   int64_t off = 0;
   auto take = [&](int64_t bytes) {
@@ -2064,9 +2062,26 @@ static hsk_embw hsk_embw_carve(void* base, int64_t n_rows, int64_t n) {
   return w;
 }
 
+// the item sort of the fused step, on a throw-away state that only says "n_keys keys, nothing lazy, no timing"
+int hsk_keysort_run(const hsk_keysort& e, int64_t n_keys, int64_t n, hipStream_t stream) {
+  hsk_bprmf_state fake;
+  memset(&fake, 0, sizeof(fake));
+  fake.n_items = n_keys;
+  hsk_ws w;
+  memset(&w, 0, sizeof(w));
+  w.it32 = e.it32;
+  w.perm1 = e.perm1;
+  w.perm = e.perm;
+  w.hist = e.hist;
+  w.btot = e.btot;
+  w.bstart = e.bstart;
+  w.offsets = e.offsets;
+  return hsk_launch_sort(&fake, w, n, stream);
+}
+
 extern "C" int64_t hsk_embedding_backward_ws_bytes(int64_t n_rows, int64_t n) {
-  if (n_rows <= 0 || n <= 0 || n >= 0x7fffffff || hsk_sort_hist_elems(n_rows, n) < 0) return -1;
-  return hsk_embw_carve(nullptr, n_rows, n).total;
+  if (!hsk_keysort_supported(n_rows, n)) return -1;
+  return hsk_keysort_carve(nullptr, n_rows, n).total;
 }
 
 extern "C" int hsk_embedding_backward(const float* grad_out, const int64_t* idx, int64_t n, int64_t n_rows, int64_t dim,
@@ -2079,25 +2094,10 @@ extern "C" int hsk_embedding_backward(const float* grad_out, const int64_t* idx,
   HSK_REQUIRE(ws_bytes >= need && ((uintptr_t)ws & 255) == 0, HSK_ERR_INVALID, "workspace: %lld bytes needed, %lld given",
               (long long)need, (long long)ws_bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  const hsk_embw e = hsk_embw_carve(ws, n_rows, n);
+  const hsk_keysort e = hsk_keysort_carve(ws, n_rows, n);
   k_idx_to_i32<<<(unsigned)hsk_ceil_div(n, 256), 256, 0, stream>>>(idx, (int)n, (int)n_rows, e.it32, status);
   HSK_LAUNCH_CHECK();
-  // the item sort of the fused step, on a throw-away state that only says "n_rows keys, nothing lazy, no timing"
-  hsk_bprmf_state fake;
-  memset(&fake, 0, sizeof(fake));
-  fake.n_items = n_rows;
-  hsk_ws w;
-  memset(&w, 0, sizeof(w));
-  w.it32 = e.it32;
-  w.perm1 = e.perm1;
-  w.perm = e.perm;
-  w.hist = e.hist;
-  w.btot = e.btot;
-  w.bstart = e.bstart;
-  w.offsets = e.offsets;
-  hsk_bprmf_state* st = &fake;   // HSK_STAGE reads st->timing (NULL here)
-  (void)st;
-  int rc = hsk_launch_sort(&fake, w, n, stream);
+  int rc = hsk_keysort_run(e, n_rows, n, stream);
   if (rc) return rc;
   rc = hsk_dispatch_dim(dim, [&](auto v_, auto n_, auto f_) {
     constexpr int V = decltype(v_)::value;

@@ -9,6 +9,7 @@ import typing
 
 from hassaku_amd.algorithms.algorithms_utils import AlgorithmsEnum
 from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm, SparseMatrixBasedRecommenderAlgorithm
+from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
 from hassaku_amd.conf.conf_parser import parse_conf, parse_conf_file, save_yaml
 from hassaku_amd.data.data_utils import DatasetsEnum, get_dataloader
 from hassaku_amd.data.dataset import TrainRecDataset
@@ -109,7 +110,11 @@ def run_test(alg: AlgorithmsEnum, dataset: DatasetsEnum, conf: typing.Union[str,
     if wandb is not None:
         wandb.init(config=conf, tags=[alg.name, dataset.name], name=conf['time_run'], job_type='test', reinit=True)
     test_loader = get_dataloader(conf, 'test')
-    model = alg.value.build_from_conf(conf, test_loader.dataset)
+    if issubclass(alg.value, DeepMatrixFactorization):
+        # its towers read the train matrix, which the test split does not hold (experiment_helper.py:103-106)
+        model = alg.value.build_from_conf(conf, TrainRecDataset(conf['dataset_path']))
+    else:
+        model = alg.value.build_from_conf(conf, test_loader.dataset)
     if isinstance(model, SparseMatrixBasedRecommenderAlgorithm):
         device = model.device
     else:

@@ -228,6 +228,74 @@ def embedding(table: torch.Tensor, idx: torch.Tensor, status=None) -> torch.Tens
     return _Embedding.apply(table, idx.contiguous(), status)
 
 
+SPARSE_ROWS_MAX_DIM = {0: 2048, 2: 1024, 1: 512, 3: 512}   # dim % 4 -> widest row hsk_dispatch_dim serves: 64 V 8
+
+
+def sparse_rows_max_dim(dim: int) -> int:
+    """The widest `dim` with dim's alignment that hsk_sparse_rows_sum serves (hsk_dispatch_dim's limit)."""
+    return SPARSE_ROWS_MAX_DIM[dim % 4]
+
+
+class _SparseRowsSum(torch.autograd.Function):
+    """out[j] = sum of Wt[c] over the stored entries c of CSR row idx[j] (hsk_sparse_rows_sum): a 0/1 row times a
+    linear layer whose weight is kept transposed.  backward = hsk_sparse_rows_sum_backward: dense gradient of Wt, terms
+    added in ascending position, deterministic.  One host read-back (the batch's entry count) per backward."""
+
+    @staticmethod
+    def forward(ctx, Wt, indptr, indices, idx, status):
+        _lib.require_gpu()
+        lib = _lib.load()
+        _chk(Wt, torch.float32, 'Wt')
+        if Wt.dim() != 2:
+            raise ValueError(f'Wt has shape {tuple(Wt.shape)}, expected [n_in, dim]')
+        n_rows = indptr.numel() - 1
+        _chk(indptr, torch.int64, 'indptr', (n_rows + 1,))
+        _chk(indices, torch.int32, 'indices')
+        _chk(idx, torch.int64, 'row indices')
+        if n_rows < 1:
+            raise ValueError('the CSR has no rows')
+        n_in, dim = Wt.shape
+        flat = idx.reshape(-1)
+        out = torch.empty((flat.numel(), dim), dtype=torch.float32, device=Wt.device)
+        _lib.check(lib.hsk_sparse_rows_sum(_p(Wt), n_in, dim, _p(indptr), _p(indices), n_rows, _p(flat), flat.numel(),
+                                           _p(out), _p(status), _stream()), 'hsk_sparse_rows_sum')
+        ctx.save_for_backward(indptr, indices, flat)
+        ctx.shape, ctx.status = (n_in, dim, n_rows), status
+        return out.view(tuple(idx.shape) + (dim,))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        indptr, indices, flat = ctx.saved_tensors
+        n_in, dim, n_rows = ctx.shape
+        n = flat.numel()
+        g = grad_out.reshape(-1, dim).contiguous()
+        grad_Wt = torch.empty((n_in, dim), dtype=torch.float32, device=g.device)
+        pair_off, n_pairs = None, 0
+        if n:
+            pair_off = torch.empty(n + 1, dtype=torch.int64, device=g.device)
+            _lib.check(lib.hsk_sparse_rows_offsets(_p(indptr), n_rows, _p(flat), n, _p(pair_off), _p(ctx.status),
+                                                   _stream()), 'hsk_sparse_rows_offsets')
+            n_pairs = int(pair_off[n].item())   # the one read-back: sizes the workspace
+        nbytes = lib.hsk_sparse_rows_sum_backward_ws_bytes(n_in, n_pairs)
+        if nbytes <= 0:
+            raise ValueError(f'{n_in} input columns / {n_pairs} batch entries: too many for the deterministic sort')
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device)
+        _lib.check(lib.hsk_sparse_rows_sum_backward(_p(g), _p(indptr), _p(indices), n_rows, n_in, _p(flat), n,
+                                                    _p(pair_off), n_pairs, dim, _p(grad_Wt), _p(ws), nbytes,
+                                                    _p(ctx.status), _stream()), 'hsk_sparse_rows_sum_backward')
+        return grad_Wt, None, None, None, None
+
+
+def sparse_rows_sum(Wt: torch.Tensor, csr, idx: torch.Tensor, status=None) -> torch.Tensor:
+    """X[idx] @ Wt for a 0/1 CSR X -> idx.shape + (dim,), differentiable wrt `Wt` (dense gradient).
+    csr: (indptr int64 [n_rows + 1], indices int32[, n_cols]); a column id names a row of Wt [n_in, dim]."""
+    indptr, indices = csr[0], csr[1]
+    if len(csr) > 2 and csr[2] != Wt.shape[0]:
+        raise ValueError(f'the CSR has {csr[2]} columns, Wt {Wt.shape[0]} rows')
+    return _SparseRowsSum.apply(Wt, indptr, indices, idx.contiguous(), status)
+
+
 def adamw_dense(p, g, m, v, lr, wd, step, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS):
     """In-place dense AdamW step (step is 1-based)."""
     _lib.require_gpu()

@@ -117,6 +117,38 @@ int hsk_embedding_backward(const float* grad_out, const int64_t* idx, int64_t n,
                            float* grad_table, void* ws, int64_t ws_bytes, int32_t* status, hsk_stream_t stream);
 
 /*
+ * The sparse first layer of DeepMatrixFactorization (algorithms/sgd_alg.py:778-880): a 0/1 row of the train matrix
+ * times the first nn.Linear, as a gather-sum over the row's stored entries.  Wt fp32 [n_in, dim] row-major is the
+ * TRANSPOSED weight; (indptr int64 [n_rows_csr + 1], indices int32) is a CSR whose column ids name rows of Wt; idx
+ * int64 [n] names CSR rows.
+ *   hsk_sparse_rows_sum           out[j, :] = sum of Wt[c, :] over the entries c of row idx[j], added in stored order
+ *                                 starting from +0.0f (an empty row gives zeros); out fp32 [n, dim].
+ *   hsk_sparse_rows_offsets       pair_off int64 [n + 1] (device): pair_off[j] = entries of rows idx[0..j),
+ *                                 pair_off[n] = the batch's entry count -- the one number the caller reads back to
+ *                                 size the backward's workspace.
+ *   hsk_sparse_rows_sum_backward  grad_Wt[c, :] = sum of g[j, :] over the batch positions j whose row holds c, added
+ *                                 in ascending j (a duplicated row id counts each time); rows nobody touches are
+ *                                 exactly 0.  Deterministic: a stable sort of the (c, j) pairs, no float atomics.
+ *                                 n_pairs = pair_off[n]; ws: hsk_sparse_rows_sum_backward_ws_bytes(n_in, n_pairs)
+ *                                 (-1: n_in too large for the sort), 256-byte aligned.  A smaller n_pairs drops the
+ *                                 pairs past it, a larger one costs only space.
+ * A row id outside [0, n_rows_csr) sets HSK_STATUS_BAD_INDEX in *status and is treated as row 0; a column id outside
+ * [0, n_in) is skipped.  dim: the widest row of the wave tiles, 64 * V * 8 floats with V floats per lane: 2048 at most if dim % 4 == 0, 1024 if
+ * only even, 512 if odd (HSK_ERR_UNSUPPORTED beyond).
+ * n == 0 is a no-op (the backward zero-fills grad_Wt).
+ */
+int hsk_sparse_rows_sum(const float* Wt, int64_t n_in, int64_t dim, const int64_t* indptr, const int32_t* indices,
+                        int64_t n_rows_csr, const int64_t* idx, int64_t n, float* out, int32_t* status,
+                        hsk_stream_t stream);
+int hsk_sparse_rows_offsets(const int64_t* indptr, int64_t n_rows_csr, const int64_t* idx, int64_t n,
+                            int64_t* pair_off, int32_t* status, hsk_stream_t stream);
+int64_t hsk_sparse_rows_sum_backward_ws_bytes(int64_t n_in, int64_t n_pairs);
+int hsk_sparse_rows_sum_backward(const float* g, const int64_t* indptr, const int32_t* indices, int64_t n_rows_csr,
+                                 int64_t n_in, const int64_t* idx, int64_t n, const int64_t* pair_off, int64_t n_pairs,
+                                 int64_t dim, float* grad_Wt, void* ws, int64_t ws_bytes, int32_t* status,
+                                 hsk_stream_t stream);
+
+/*
  * One dense AdamW step on a flat parameter of n elements -- torch.optim.AdamW defaults
  * (train/trainer.py:52-53,147): p*=1-lr*wd; m=lerp(m,g,1-b1); v=b2*v+(1-b2)g^2;
  * p -= (lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps).  `step` is t (1-based, after increment).
