@@ -121,6 +121,60 @@ template <>
 __device__ __forceinline__ void hsk_stg_nt<1>(float* p, const hsk_vec<1>& x) {
   __builtin_nontemporal_store(x.v[0], p);
 }
+// write-through store (sc1): the line leaves the XCD's L2 with the store instead of staying there dirty -- for rows
+// nobody reads again inside the launch that writes them, so that they do not push the gathered hot set out.  16 bytes
+// per lane only: a narrower sc1 store is one fabric write each (2.7x / 6x the time per byte at 8 / 4 bytes).
+// `row` is WAVE-UNIFORM (one wave, one row): the buffer descriptor is built per row with that row's bytes as its
+// bound, so the byte offset stays far below 2^31 however large the table is (the cfg5 share's item table is 169 GB).
+template <int V>
+__device__ __forceinline__ void hsk_stg_wt(float* row, int off, int row_floats, const hsk_vec<V>& x) {
+  static_assert(V == 4, "write-through stores are 16 bytes per lane");
+  typedef unsigned int vu __attribute__((ext_vector_type(4)));
+  const unsigned long long a = (unsigned long long)row;
+  void* base = (void*)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                       (unsigned)__builtin_amdgcn_readfirstlane((int)a));
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, row_floats * 4, 0x00020000);
+  vu t;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t[i] = __float_as_uint(x.v[i]);
+  __builtin_amdgcn_raw_buffer_store_b128(t, rsrc, off * 4, 0, /*aux: sc1*/ 16);
+}
+
+// Cache policy of a stream of stores; which stream leaves with which is decided by the two masks below.
+enum hsk_store_policy {
+  HSK_ST_PLAIN = 0,
+  HSK_ST_NT = 1,   // non-temporal (hsk_stg_nt)
+  HSK_ST_WT = 2    // write-through (hsk_stg_wt); rows of fewer than 4 floats per lane fall back to plain stores
+};
+// One bit per stream of the large-batch step, so that each can be measured alone (-DHSK_WT_STREAMS=<mask>):
+#define HSK_STREAM_ITEM 1      // item p/m/v of the D-sliced item pass (hsk_item_sliced_body, VS = 4)
+#define HSK_STREAM_OWNER 2     // the owners' user p/m/v in the item/user launch (hsk_user_row_chunks)
+#define HSK_STREAM_DUP 4       // partial gradient rows of the partitioned forward (k_fwd_part)
+#define HSK_STREAM_UCUR 8      // ucur / mcur / vcur of the partitioned forward (hsk_user_row_current)
+#define HSK_STREAM_AHEAD 16    // p/m/v of the next batch's rows (hsk_user_ahead_body riding in k_fwd_part)
+#define HSK_STREAM_REPLAY_MV 32   // moments of rows replayed by a whole workgroup (hsk_row_replay_wg)
+#define HSK_STREAM_REPLAY_P 64    // their parameters
+#ifndef HSK_WT_STREAMS
+#define HSK_WT_STREAMS 31   // the five streams of the large-batch step: each paid alone, MEASUREMENTS.md "Write-through stores"
+#endif
+#ifndef HSK_NT_STREAMS
+#define HSK_NT_STREAMS 0   // the retired HSK_ITEM_NT = 1 is bit 1 here, HSK_REPLAY_NT = 1 / 2 bits 32 / 32 + 64: all measured, all off
+#endif
+constexpr hsk_store_policy hsk_stream_policy(int stream) {
+  return (HSK_WT_STREAMS & stream) ? HSK_ST_WT : (HSK_NT_STREAMS & stream) ? HSK_ST_NT : HSK_ST_PLAIN;
+}
+
+// x -> row[off .. off + V) under policy POL (`row` wave-uniform, `row_floats` the row's length)
+template <int POL, int V>
+__device__ __forceinline__ void hsk_stg_as(float* row, int off, int row_floats, const hsk_vec<V>& x) {
+  if constexpr (POL == HSK_ST_WT && V == 4)
+    hsk_stg_wt<4>(row, off, row_floats, x);
+  else if constexpr (POL == HSK_ST_NT)
+    hsk_stg_nt<V>(row + off, x);
+  else
+    hsk_stg<V>(row + off, x);
+}
+
 template <int V>
 __device__ __forceinline__ hsk_vec<V> hsk_zero() {
   hsk_vec<V> r;

@@ -55,7 +55,8 @@ struct hsk_part_args {
 
 // The riding phases of the forward's launch.  (Any of them in the kernel costs the gather loop's register allocation one
 // register: 129 with four item rows per buffer -- three waves per SIMD; capped at 128 it spills and the kernel runs 86 ->
-// 96 us; called out of line it needs a stack.  Hence HSK_FWD_PART_R = 3 rows per buffer: 114 registers.)
+// 96 us; called out of line it needs a stack.  Hence HSK_FWD_PART_R = 3 rows per buffer: 114 registers; 126 since the
+// write-through stores, still four waves per SIMD.)
 __device__ __forceinline__ void hsk_ride_fwd_roles(const hsk_ride_fwd& rf, int bid) {
   if (bid < rf.Bk.n_blocks) {
     __shared__ int bucket_lds[5 * HSK_PIPE_MAX_IPB + 2];
@@ -92,7 +93,7 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
     if (o < full) {
       const int k = o / period, j = o - k * period;
       if (j == pa.ahead_stride) {
-        hsk_user_ahead_body<V, NCH, FULL, GEN>(aa, k * 8 + r);
+        hsk_user_ahead_body<V, NCH, FULL, GEN, hsk_stream_policy(HSK_STREAM_AHEAD)>(aa, k * 8 + r);
         return;
       }
       bid = (k * pa.ahead_stride + j) * 8 + r;
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
     }
   } else {
     if (bid < pa.n_ahead_blocks) {
-      hsk_user_ahead_body<V, NCH, FULL, GEN>(aa, bid);
+      hsk_user_ahead_body<V, NCH, FULL, GEN, hsk_stream_policy(HSK_STREAM_AHEAD)>(aa, bid);
       return;
     }
     bid -= pa.n_ahead_blocks;
@@ -168,9 +169,10 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
   float mybias = Ib ? Ib[myidx] : 0.f;
 
   if (lz.mU)
-    hsk_user_row_current<V, NCH, FULL>(ur, u, b, B, D, lane, lz, q == 0, hsk_uniform_i(done_v), hsk_uniform_i(own_v));
+    hsk_user_row_current<V, NCH, FULL, hsk_stream_policy(HSK_STREAM_UCUR)>(ur, u, b, B, D, lane, lz, q == 0,
+                                                                           hsk_uniform_i(done_v), hsk_uniform_i(own_v));
   else if (lz.ucur && q == 0)
-    hsk_row_store<V, NCH, FULL>(ur, lz.ucur + (long long)b * D, lane, D);
+    hsk_row_store_as<hsk_stream_policy(HSK_STREAM_UCUR), V, NCH, FULL>(ur, lz.ucur + (long long)b * D, lane, D);
   hsk_row_zero(acc);
   const float s0 = hsk_wave_sum(hsk_row_dot_partial(ur, r0)) + bias0;
 
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
     if (q == 0 && lane == 0) lsum += (double)hsk_softplus(-s0);
   }
   hsk_row_axpy(acc, -gp, r0);
-  hsk_row_store<V, NCH, FULL>(acc, dUp + ((long long)b * P + q) * D, lane, D);   // [b][q][D]
+  hsk_row_store_as<hsk_stream_policy(HSK_STREAM_DUP), V, NCH, FULL>(acc, dUp + ((long long)b * P + q) * D, lane, D);   // [b][q][D]
   const double l = hsk_wave_sum_f64(lsum);
   if (lane == 0) {
     g_s[(long long)b * K + q] = -gp;

@@ -18,28 +18,18 @@
 // 4 against 8 elsewhere: lfm2b-shaped training 509 against 560 us, the cfg5 share's item pass 6.26 against 6.38 ms
 #define HSK_ITEM_MLP 4
 #endif
-#ifndef HSK_ITEM_NT
-#define HSK_ITEM_NT 0      // 1: the item rows (p, m, v: read once, written once per step) move with non-temporal hints
-#endif
+// The item rows (p, m, v) are read once and written once per step: a stream with a store policy of its own
+// (HSK_STREAM_ITEM, hsk_common.h); under the non-temporal policy the loads carry the hint too.
 template <int VS>
 __device__ __forceinline__ hsk_vec<VS> hsk_ldg_stream(const float* p) {
-#if HSK_ITEM_NT
-  hsk_vec<VS> r;
+  if constexpr (hsk_stream_policy(HSK_STREAM_ITEM) == HSK_ST_NT) {
+    hsk_vec<VS> r;
 #pragma unroll
-  for (int i = 0; i < VS; ++i) r.v[i] = __builtin_nontemporal_load(p + i);
-  return r;
-#else
-  return hsk_ldg<VS>(p);
-#endif
-}
-template <int VS>
-__device__ __forceinline__ void hsk_stg_stream(float* p, const hsk_vec<VS>& x) {
-#if HSK_ITEM_NT
-#pragma unroll
-  for (int i = 0; i < VS; ++i) __builtin_nontemporal_store(x.v[i], p + i);
-#else
-  hsk_stg<VS>(p, x);
-#endif
+    for (int i = 0; i < VS; ++i) r.v[i] = __builtin_nontemporal_load(p + i);
+    return r;
+  } else {
+    return hsk_ldg<VS>(p);
+  }
 }
 
 #ifdef HSK_DEBUG_XCC
@@ -169,9 +159,12 @@ __device__ __forceinline__ void hsk_item_sliced_body(const hsk_item_args& a, int
       if (live) {
 #pragma unroll
         for (int q = 0; q < VS; ++q) hsk_adamw_update<GEN>(p.v[q], m.v[q], v.v[q], acc.v[q], c);
-        hsk_stg_stream<VS>(Iw + (long long)i * D + d, p);
-        hsk_stg_stream<VS>(mI + (long long)i * D + d, m);
-        hsk_stg_stream<VS>(vI + (long long)i * D + d, v);
+        // (the lazy list's instantiations keep plain stores: the descriptor's scalar registers cost the stand-alone
+        // k_item_update_sliced<.., LAZY> a wave per SIMD, and their tables are the ones no cache holds anyway)
+        constexpr int POL = LAZY ? HSK_ST_PLAIN : hsk_stream_policy(HSK_STREAM_ITEM);
+        hsk_stg_as<POL, VS>(Iw + (long long)i * D, d, D, p);
+        hsk_stg_as<POL, VS>(mI + (long long)i * D, d, D, m);
+        hsk_stg_as<POL, VS>(vI + (long long)i * D, d, D, v);
       }
       if (slice == 0 && Ib) {
         const float gbias = hsk_wave_sum(gb_lane);
@@ -317,6 +310,9 @@ template <int V, int NCH, bool FULL, int VS, bool GEN, bool LAZYI, bool PART = f
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_item_user(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks, int dense_users, hsk_ahead_args aa,
                  int n_ahead_blocks, hsk_ride_item ri = hsk_ride_item{}) {
+  // store policies (hsk_common.h).  The LAZYI instantiations keep plain stores throughout: their tables are the ones no
+  // cache holds, and the descriptors' scalar registers cost the spilling ones among them more scratch.
+  constexpr int POL_OWNER = LAZYI ? HSK_ST_PLAIN : hsk_stream_policy(HSK_STREAM_OWNER);
   int bid = (int)blockIdx.x;
   if (PART) {   // preparation phases of later batches riding in this launch (hsk_fwd_part.h: hsk_ride_item)
     if (bid < ri.n_total) {
@@ -332,9 +328,9 @@ void k_item_user(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks, int
   }
   if (bid < n_user_blocks) {
     if (dense_users)
-      hsk_user_update_dense_body<V, NCH, FULL, GEN, PART>(ua, bid);
+      hsk_user_update_dense_body<V, NCH, FULL, GEN, PART, POL_OWNER>(ua, bid);
     else
-      hsk_user_update_lazy_body<V, NCH, FULL, GEN, PART>(ua, bid);
+      hsk_user_update_lazy_body<V, NCH, FULL, GEN, PART, POL_OWNER>(ua, bid);
     return;
   }
   if (LAZYI && bid < n_user_blocks + n_ahead_blocks) {

@@ -73,6 +73,20 @@ __device__ __forceinline__ void hsk_row_store(const hsk_row<V, NCH>& r, float* _
   }
 }
 
+// the same under a store policy (hsk_common.h); `base` is wave-uniform, as everywhere a wave owns a row
+template <int POL, int V, int NCH, bool FULL>
+__device__ __forceinline__ void hsk_row_store_as(const hsk_row<V, NCH>& r, float* __restrict__ base, int lane, int D) {
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const int off = (c * 64 + lane) * V;
+    if (FULL || off < D) hsk_stg_as<POL, V>(base, off, D, r.c[c]);
+  }
+}
+template <int V, int NCH, bool FULL>
+__device__ __forceinline__ void hsk_row_store_wt(const hsk_row<V, NCH>& r, float* __restrict__ base, int lane, int D) {
+  hsk_row_store_as<HSK_ST_WT, V, NCH, FULL>(r, base, lane, D);
+}
+
 template <int V, int NCH>
 __device__ __forceinline__ void hsk_row_zero(hsk_row<V, NCH>& r) {
 #pragma unroll

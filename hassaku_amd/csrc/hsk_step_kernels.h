@@ -2,11 +2,9 @@
 #pragma once
 #include "hsk_rows.h"
 
-#ifndef HSK_REPLAY_NT
-#define HSK_REPLAY_NT 0   // 1 / 2: moments / whole rows of replayed rows leave with non-temporal stores (hsk_stg_nt).
-                          // Measured at the hbm shape (forward behind the lazy item catch-up): 216 -> 210 us forward,
-                          // the catch-up itself slower: off.
-#endif
+// Store policies of the streams of this file: hsk_stream_policy (hsk_common.h).  The replayed rows of hsk_row_replay_wg
+// were measured with non-temporal stores at the hbm shape (forward behind the lazy item catch-up): 216 -> 210 us forward,
+// the catch-up itself slower: off.
 
 __device__ __forceinline__ hsk_adamw_consts hsk_consts_at(const hsk_adamw_consts& base, const float2* __restrict__ tab,
                                                           int tab_len, int t) {
@@ -81,7 +79,7 @@ struct hsk_lazy_user_args {
 #define HSK_DUP_MAX 8   // duplicate entries of one user that are listed for the owner (more: batch scan)
 
 // `done` / `own`: last_step[u] and owner[u], loaded by the caller (early, together with its other loads)
-template <int V, int NCH, bool FULL>
+template <int V, int NCH, bool FULL, int POL = HSK_ST_PLAIN>
 __device__ __forceinline__ void hsk_user_row_current(hsk_row<V, NCH>& p, int u, int b, int B, int D, int lane,
                                                      const hsk_lazy_user_args& lz, bool publish, int done, int own) {
   const int step = lz.desc ? lz.desc->step0 + lz.rel + 1 : lz.step;
@@ -108,12 +106,12 @@ __device__ __forceinline__ void hsk_user_row_current(hsk_row<V, NCH>& p, int u, 
       }
     }
     if (publish && own == b) {
-      hsk_row_store<V, NCH, FULL>(m, lz.mcur + (long long)b * D, lane, D);
-      hsk_row_store<V, NCH, FULL>(v, lz.vcur + (long long)b * D, lane, D);
+      hsk_row_store_as<POL, V, NCH, FULL>(m, lz.mcur + (long long)b * D, lane, D);
+      hsk_row_store_as<POL, V, NCH, FULL>(v, lz.vcur + (long long)b * D, lane, D);
     }
   }
   if (!publish) return;
-  hsk_row_store<V, NCH, FULL>(p, lz.ucur + (long long)b * D, lane, D);
+  hsk_row_store_as<POL, V, NCH, FULL>(p, lz.ucur + (long long)b * D, lane, D);
   if (lane == 0) {
     if (own != b && own >= 0 && own < B) {   // a further entry of a user somebody else owns: tell the owner
       const int slot = atomicAdd(&lz.dupcnt[own], 1);
@@ -522,19 +520,10 @@ __device__ __forceinline__ void hsk_row_replay_wg(float* __restrict__ prow, floa
       }
     }
     if (live) {
-#if HSK_REPLAY_NT > 1
-      hsk_stg_nt<VV>(prow + d0, p);
-#else
-      hsk_stg<VV>(prow + d0, p);
-#endif
+      hsk_stg_as<hsk_stream_policy(HSK_STREAM_REPLAY_P), VV>(prow, d0, D, p);
       if (!P_ONLY) {
-#if HSK_REPLAY_NT
-        hsk_stg_nt<VV>(mrow + d0, m);
-        hsk_stg_nt<VV>(vrow + d0, v);
-#else
-        hsk_stg<VV>(mrow + d0, m);
-        hsk_stg<VV>(vrow + d0, v);
-#endif
+        hsk_stg_as<hsk_stream_policy(HSK_STREAM_REPLAY_MV), VV>(mrow, d0, D, m);
+        hsk_stg_as<hsk_stream_policy(HSK_STREAM_REPLAY_MV), VV>(vrow, d0, D, v);
       }
     }
   }
@@ -755,7 +744,8 @@ __device__ __forceinline__ void hsk_resolve_step(const hsk_step_desc* desc, int 
 // workgroups that share the launch their occupancy).  Gradient = dUb[b] + the rows of the user's further entries in
 // the batch (n entries in all), added in ascending b: usually those registered with the owner (dupcnt / duplist, in
 // arrival order: ranked here), otherwise the batch is scanned.  n == 0: no gradient (dense sweep over an idle row).
-template <int V, int NCH, bool FULL, bool GEN, bool PART = false>
+// POL: store policy of the rewritten (p, m, v)
+template <int V, int NCH, bool FULL, bool GEN, bool PART = false, int POL = HSK_ST_PLAIN>
 __device__ __forceinline__ void hsk_user_row_chunks(const hsk_user_lazy_args& a, int row, int b, int n,
                                                     const float* __restrict__ psrc, const float* __restrict__ msrc,
                                                     const float* __restrict__ vsrc, float* __restrict__ prow,
@@ -822,14 +812,14 @@ __device__ __forceinline__ void hsk_user_row_chunks(const hsk_user_lazy_args& a,
 #pragma unroll
     for (int q = 0; q < V; ++q) hsk_adamw_update<GEN>(p.v[q], m.v[q], v.v[q], g.v[q], a.c);
     if (live) {
-      hsk_stg<V>(prow + off, p);
-      hsk_stg<V>(mrow + off, m);
-      hsk_stg<V>(vrow + off, v);
+      hsk_stg_as<POL, V>(prow, off, D, p);
+      hsk_stg_as<POL, V>(mrow, off, D, m);
+      hsk_stg_as<POL, V>(vrow, off, D, v);
     }
   }
 }
 
-template <int V, int NCH, bool FULL, bool GEN, bool PART = false>
+template <int V, int NCH, bool FULL, bool GEN, bool PART = false, int POL = HSK_ST_PLAIN>
 __device__ __forceinline__ void hsk_user_update_lazy_body(const hsk_user_lazy_args& a0, int bid) {
   hsk_user_lazy_args a = a0;
   hsk_resolve_step(a.desc, a.rel, a.ctab, a.ctab_len, a.step, a.c);
@@ -857,7 +847,7 @@ __device__ __forceinline__ void hsk_user_update_lazy_body(const hsk_user_lazy_ar
   const float* psrc = behind ? a.ucur + (long long)b * D : prow;
   const float* msrc = behind ? a.mcur + (long long)b * D : mrow;
   const float* vsrc = behind ? a.vcur + (long long)b * D : vrow;
-  hsk_user_row_chunks<V, NCH, FULL, GEN, PART>(a, row, b, n, psrc, msrc, vsrc, prow, mrow, vrow, lane);
+  hsk_user_row_chunks<V, NCH, FULL, GEN, PART, POL>(a, row, b, n, psrc, msrc, vsrc, prow, mrow, vrow, lane);
   if (lane == 0) {
     if (a.Ub) {
       float pb = a.Ub[row], mb = a.mUb[row], vb = a.vUb[row];
@@ -885,7 +875,7 @@ __global__ __launch_bounds__(256) void k_user_update_lazy(hsk_user_lazy_args a, 
 // Dense mode (small user tables: the sweep is cheaper than replaying): AdamW on EVERY row of the table, the batch
 // rows with their gradient (owner map, duplicates by batch scan), all others with g = 0 -- torch.optim's own order of
 // operations.  One wave per table row; workgroup ceil(n_users/4) runs hsk_finish_block.
-template <int V, int NCH, bool FULL, bool GEN, bool PART = false>
+template <int V, int NCH, bool FULL, bool GEN, bool PART = false, int POL = HSK_ST_PLAIN>
 __device__ __forceinline__ void hsk_user_update_dense_body(const hsk_user_lazy_args& a0, int bid) {
   hsk_user_lazy_args a = a0;
   hsk_resolve_step(a.desc, a.rel, a.ctab, a.ctab_len, a.step, a.c);
@@ -904,7 +894,7 @@ __device__ __forceinline__ void hsk_user_update_dense_body(const hsk_user_lazy_a
   const int b0 = n > 0 ? hsk_uniform_i(a.owner[row]) : 0;
   hsk_user_lazy_args a2 = a;
   a2.dupcnt = nullptr;   // the dense path never registered duplicates: batch scan
-  hsk_user_row_chunks<V, NCH, FULL, GEN, PART>(a2, row, b0, n, prow, mrow, vrow, prow, mrow, vrow, lane);
+  hsk_user_row_chunks<V, NCH, FULL, GEN, PART, POL>(a2, row, b0, n, prow, mrow, vrow, prow, mrow, vrow, lane);
   if (n > 0 && lane == 0) {
     a.owner[row] = HSK_OWNER_NONE;
     a.cnt[row] = 0;
@@ -950,7 +940,7 @@ struct hsk_ahead_args {
 };
 
 // One WAVE per entry of the next batch (4 per workgroup): a wave slot is what these workgroups take from the item pass.
-template <int V, int NCH, bool FULL, bool GEN>
+template <int V, int NCH, bool FULL, bool GEN, int POL = HSK_ST_PLAIN>
 __device__ __forceinline__ void hsk_user_ahead_body(const hsk_ahead_args& a, int bid) {
   const int lane = hsk_lane();
   const int b = bid * 4 + hsk_uniform_i(threadIdx.x >> 6);
@@ -990,9 +980,9 @@ __device__ __forceinline__ void hsk_user_ahead_body(const hsk_ahead_args& a, int
         for (int q = 0; q < V; ++q) hsk_adamw_replay<GEN>(p.c[cc].v[q], m.c[cc].v[q], v.c[cc].v[q], ct);
     }
   }
-  hsk_row_store<V, NCH, FULL>(p, prow, lane, D);
-  hsk_row_store<V, NCH, FULL>(m, mrow, lane, D);
-  hsk_row_store<V, NCH, FULL>(v, vrow, lane, D);
+  hsk_row_store_as<POL, V, NCH, FULL>(p, prow, lane, D);
+  hsk_row_store_as<POL, V, NCH, FULL>(m, mrow, lane, D);
+  hsk_row_store_as<POL, V, NCH, FULL>(v, vrow, lane, D);
   if (lane == 0) {
     if (a.Ub) {
       float pb = a.Ub[u], mb = a.mUb[u], vb = a.vUb[u];
