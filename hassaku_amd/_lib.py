@@ -104,6 +104,10 @@ SIGNATURES = {
     'hsk_bprmf_train_steps': (c_int, [POINTER(HskBprmfState), c_void_p, c_int64, c_int64, c_int64, c_int64,
                                       c_void_p]),
     'hsk_bprmf_last_sort': (c_int, [POINTER(HskBprmfState), c_int64, c_void_p, c_void_p, c_void_p]),
+    'hsk_key_sort_plan': (c_int, [c_int64, c_int64, c_int, POINTER(c_int64)]),
+    'hsk_key_sort_ws_bytes': (c_int64, [c_int64, c_int64, c_int]),
+    'hsk_key_sort': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_int64, c_void_p, c_void_p]),
     'hsk_bprmf_graph_replays': (c_int64, [POINTER(HskBprmfState)]),
     'hsk_bprmf_batch_columns': (c_int64, [POINTER(HskBprmfState), c_int64, c_int64]),
     'hsk_eval_set_arith': (None, [c_int]),

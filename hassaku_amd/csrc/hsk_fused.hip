@@ -284,8 +284,10 @@ static int hsk_check_state(const hsk_bprmf_state* st) {
   const int64_t need = st->ws_sharded
                            ? hsk_shard_base_workspace_bytes(st->n_users, st->n_items, st->dim, st->max_batch, st->max_cols)
                            : hsk_bprmf_workspace_bytes(st->n_users, st->n_items, st->dim, st->max_batch, st->max_cols);
-  HSK_REQUIRE(need > 0, HSK_ERR_UNSUPPORTED, "n_items %lld too large for the item sort (max %d per device)",
-              (long long)st->n_items, HSK_SORT_MAX_BUCKETS * HSK_SORT_MAX_IPB);
+  // (the workspace size knows no lazy_items: it refuses what no state can sort, the second test the rest)
+  HSK_REQUIRE(need > 0 && st->n_items <= hsk_sort_max_keys(st->lazy_items != 0), HSK_ERR_UNSUPPORTED,
+              "n_items %lld too large for the item sort (max %lld per device%s)", (long long)st->n_items,
+              (long long)hsk_sort_max_keys(st->lazy_items != 0), st->lazy_items ? " with lazy_items" : "");
   HSK_REQUIRE(st->workspace_bytes >= need, HSK_ERR_INVALID, "workspace too small: %lld < %lld",
               (long long)st->workspace_bytes, (long long)need);
   HSK_REQUIRE(((uintptr_t)st->workspace & 255) == 0, HSK_ERR_INVALID, "workspace must be 256-byte aligned");
@@ -861,27 +863,26 @@ static inline bool hsk_capturing(const hsk_bprmf_state* st);
 static int hsk_launch_sort(const hsk_bprmf_state* st, const hsk_ws& w, int64_t total, hipStream_t stream,
                            const int* n_dev = nullptr) {
   const int I = (int)st->n_items;
-  if (hsk_sort_lds_fits(I, total)) {
+  const hsk_sort_choice sc = hsk_choose_sort(st->n_items, total, st->lazy_items != 0);
+  HSK_REQUIRE(sc.kind != HSK_SORT_UNSUPPORTED, HSK_ERR_UNSUPPORTED, "item sort: n_items too large");
+  int* tl = st->lazy_items ? w.touched : nullptr;
+  int* tn = st->lazy_items ? w.n_touched : nullptr;
+  if (sc.kind == HSK_SORT_LDS) {
     // one workgroup, LDS cursors + per-item fix-up (see k_sort_lds)
-    const size_t lds = hsk_sort_lds_bytes(I);
+    const size_t lds = sc.lds_bytes;
     if (lds > 65536 && !hsk_capturing(st))   // opt-in for > 64 KB of dynamic LDS (not a stream operation)
       HSK_HIP(hipFuncSetAttribute((const void*)k_sort_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HSK_STAGE(HSK_STAGE_SCATTER, (k_sort_lds<<<1, 1024, lds, stream>>>(w.it32, (int)total, I, w.perm, w.offsets,
-                                                                       st->lazy_items ? w.touched : nullptr,
-                                                                       st->lazy_items ? w.n_touched : nullptr, n_dev)));
+    HSK_STAGE(HSK_STAGE_SCATTER, (k_sort_lds<<<1, 1024, lds, stream>>>(w.it32, (int)total, I, w.perm, w.offsets, tl, tn, n_dev)));
     HSK_LAUNCH_CHECK();
     return HSK_OK;
   }
-  if (total <= 1024 * 8) {
+  if (sc.kind != HSK_SORT_TWO_LEVEL) {
     // one workgroup sorts the whole batch (see k_sort_small)
-    int nbits = 1;
-    while ((1ll << nbits) <= (long long)I) ++nbits;   // keys 0..I (I = padding) fit
-    int* tl = st->lazy_items ? w.touched : nullptr;
-    int* tn = st->lazy_items ? w.n_touched : nullptr;
+    const int nbits = sc.nbits;
     HSK_STAGE(HSK_STAGE_SCATTER, {
-      if (total <= 1024 * 2)
+      if (sc.kind == HSK_SORT_SMALL2)
         k_sort_small<2><<<1, 1024, 0, stream>>>(w.it32, (int)total, I, nbits, w.perm, w.offsets, tl, tn, n_dev);
-      else if (total <= 1024 * 4)
+      else if (sc.kind == HSK_SORT_SMALL4)
         k_sort_small<4><<<1, 1024, 0, stream>>>(w.it32, (int)total, I, nbits, w.perm, w.offsets, tl, tn, n_dev);
       else
         k_sort_small<8><<<1, 1024, 0, stream>>>(w.it32, (int)total, I, nbits, w.perm, w.offsets, tl, tn, n_dev);
@@ -889,9 +890,8 @@ static int hsk_launch_sort(const hsk_bprmf_state* st, const hsk_ws& w, int64_t t
     HSK_LAUNCH_CHECK();
     return HSK_OK;
   }
-  hsk_sort_plan plan;
-  HSK_REQUIRE(hsk_make_sort_plan(I, total, &plan) == 0, HSK_ERR_UNSUPPORTED, "item sort: n_items too large");
-  const size_t bucket_lds = ((size_t)(st->lazy_items ? 6 : 5) * plan.ipb + 2) * sizeof(int);
+  const hsk_sort_plan& plan = sc.plan;
+  const size_t bucket_lds = sc.lds_bytes;
   if (bucket_lds > 65536)
     HSK_HIP(hipFuncSetAttribute((const void*)k_sort_bucket, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bucket_lds));
   if (st->lazy_items) HSK_HIP(hipMemsetAsync(w.n_touched, 0, sizeof(int), stream));
@@ -1296,10 +1296,10 @@ static bool hsk_pipe_plan(const hsk_bprmf_state* st, int64_t batch, int64_t n_ne
   const int64_t total = batch * hsk_part_cols(n_neg + 1, n_part);
   if (n_part_out) *n_part_out = n_part;
   if (total_out) *total_out = total;
-  if (n_part <= 1 || hsk_sort_lds_fits(st->n_items, total) || total <= 1024 * 8) return false;
-  hsk_sort_plan p;
-  if (hsk_make_sort_plan(st->n_items, total, &p) != 0 || p.ipb > HSK_PIPE_MAX_IPB) return false;
-  if (plan) *plan = p;
+  if (n_part <= 1) return false;
+  const hsk_sort_choice sc = hsk_choose_sort(st->n_items, total, false);   // (lazy_items: not eligible)
+  if (sc.kind != HSK_SORT_TWO_LEVEL || sc.plan.ipb > HSK_PIPE_MAX_IPB) return false;
+  if (plan) *plan = sc.plan;
   return true;
 }
 
@@ -1337,7 +1337,7 @@ static int hsk_pipe_launch_phase(const hsk_bprmf_state* st, const hsk_ws& w, con
                                                                                    w.perm1, w.bstart, nullptr);
       break;
     default:
-      k_sort_bucket<<<(unsigned)plan.n_buckets, 256, (5 * (size_t)plan.ipb + 2) * sizeof(int), stream>>>(
+      k_sort_bucket<<<(unsigned)plan.n_buckets, 256, hsk_sort_bucket_lds_bytes(plan.ipb, false), stream>>>(
           w.perm1, (int)total, I, plan, w.bstart, w.perm, w.offsets, nullptr, nullptr, nullptr);
   }
   HSK_LAUNCH_CHECK();
@@ -1617,17 +1617,12 @@ static int hsk_capture_steps(hsk_bprmf_state* st, const hsk_ws& w, int64_t n, in
   hsk_aux* aux = (hsk_aux*)st->aux;
   hipStream_t stream = aux->cap;
   const int64_t K = n_neg + 1, total = batch * K;
-  if (hsk_sort_lds_fits(st->n_items, total)) {
-    if (hsk_sort_lds_bytes(st->n_items) > 65536)
-      HSK_HIP(hipFuncSetAttribute((const void*)k_sort_lds, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)hsk_sort_lds_bytes(st->n_items)));
-  } else if (total > 1024 * 8) {   // dynamic-LDS opt-in of the bucket sort: not a stream operation, do it before the capture
-    hsk_sort_plan plan;
-    HSK_REQUIRE(hsk_make_sort_plan((int)st->n_items, total, &plan) == 0, HSK_ERR_UNSUPPORTED, "item sort: n_items too large");
-    const size_t bucket_lds = ((size_t)(st->lazy_items ? 6 : 5) * plan.ipb + 2) * sizeof(int);
-    if (bucket_lds > 65536)
-      HSK_HIP(hipFuncSetAttribute((const void*)k_sort_bucket, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bucket_lds));
-  }
+  // dynamic-LDS opt-in of k_sort_lds / the bucket sort: not a stream operation, do it before the capture
+  const hsk_sort_choice sc = hsk_choose_sort(st->n_items, total, st->lazy_items != 0);
+  HSK_REQUIRE(sc.kind != HSK_SORT_UNSUPPORTED, HSK_ERR_UNSUPPORTED, "item sort: n_items too large");
+  if (sc.lds_bytes > 65536)
+    HSK_HIP(hipFuncSetAttribute(sc.kind == HSK_SORT_LDS ? (const void*)k_sort_lds : (const void*)k_sort_bucket,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sc.lds_bytes));
   const int64_t step_saved = st->step;
   const int set_saved = aux->cur_set, slot_saved = aux->cur_slot;
   const int timing_saved = st->timing_now;
@@ -1644,7 +1639,7 @@ static int hsk_capture_steps(hsk_bprmf_state* st, const hsk_ws& w, int64_t n, in
   // Grouped preparation: the batches of G consecutive steps are sampled and sorted by one launch each -- group 0 on the
   // main stream at the head of the run, group i+1 on the side stream from the first step of group i on; the steps
   // themselves launch no prefetch.  (k_sort_lds shapes only: one workgroup per batch.)
-  const int G = (!st->lazy_items && hsk_sort_lds_fits(st->n_items, total)) ? std::min<int64_t>(w.group, n) : 1;
+  const int G = (!st->lazy_items && sc.kind == HSK_SORT_LDS) ? std::min<int64_t>(w.group, n) : 1;
   auto prepare_group = [&](int gset, int64_t first, hipStream_t q) -> int {
     const hsk_ws wg = hsk_select(w, gset);
     const int cnt_g = (int)std::min<int64_t>(G, n - first);
@@ -1652,7 +1647,7 @@ static int hsk_capture_steps(hsk_bprmf_state* st, const hsk_ws& w, int64_t n, in
         st->coo_user, st->coo_item, (int)batch, (int)n_neg, st->csr_indptr, st->csr_indices, (int)st->n_items, st->seed,
         wg.u32, wg.it32, wg.owner, wg.cnt, st->status, hsk_alias{st->alias_prob, st->alias_idx}, w.desc, (int)first,
         wg.stamp, cnt_g, (long long)w.gs_batch, (long long)w.gs_ent, (long long)w.gs_users);
-    k_sort_lds<<<(unsigned)cnt_g, 1024, hsk_sort_lds_bytes(st->n_items), q>>>(
+    k_sort_lds<<<(unsigned)cnt_g, 1024, sc.lds_bytes, q>>>(
         wg.it32, (int)total, (int)st->n_items, wg.perm, wg.offsets, nullptr, nullptr, nullptr, (long long)w.gs_ent,
         (long long)w.gs_items);
     return hipGetLastError() == hipSuccess ? HSK_OK : HSK_ERR_HIP;
@@ -1828,7 +1823,8 @@ extern "C" int hsk_bprmf_train_steps(hsk_bprmf_state* st, const int64_t* order, 
       aux->graph_launches += 1;
       st->step += n;
       {
-        const int Gr = (!st->lazy_items && hsk_sort_lds_fits(st->n_items, batch * (n_neg + 1))) ? (int)std::min<int64_t>(w.group, n) : 1;
+        const bool lds_sort = hsk_choose_sort(st->n_items, batch * (n_neg + 1), false).kind == HSK_SORT_LDS;
+        const int Gr = (!st->lazy_items && lds_sort) ? (int)std::min<int64_t>(w.group, n) : 1;
         if (Gr > 1) {   // grouped preparation: the last batch sits in slot (n-1) % G of set (set0 + (n-1)/G) & 1
           aux->cur_set = (set0 + (int)((n - 1) / Gr)) & 1;
           aux->cur_slot = (int)((n - 1) % Gr);
@@ -2038,7 +2034,7 @@ extern "C" int hsk_embedding_gather(const float* table, int64_t n_rows, int64_t 
 }
 
 bool hsk_keysort_supported(int64_t n_keys, int64_t n) {
-  return n_keys > 0 && n > 0 && n < 0x7fffffff && hsk_sort_hist_elems(n_keys, n) >= 0;
+  return n > 0 && hsk_choose_sort(n_keys, n, false).kind != HSK_SORT_UNSUPPORTED;
 }
 
 hsk_keysort hsk_keysort_carve(void* base, int64_t n_rows, int64_t n) {
@@ -2062,11 +2058,14 @@ hsk_keysort hsk_keysort_carve(void* base, int64_t n_rows, int64_t n) {
   return w;
 }
 
-// the item sort of the fused step, on a throw-away state that only says "n_keys keys, nothing lazy, no timing"
-int hsk_keysort_run(const hsk_keysort& e, int64_t n_keys, int64_t n, hipStream_t stream) {
+// the item sort of the fused step, on a throw-away state that only says "n_keys keys, no timing" -- and, with a
+// touched list to fill, "lazy items"; n_dev: see hsk_launch_sort
+static int hsk_keysort_run_with(const hsk_keysort& e, int64_t n_keys, int64_t n, hipStream_t stream, int* touched,
+                                int* n_touched, const int* n_dev) {
   hsk_bprmf_state fake;
   memset(&fake, 0, sizeof(fake));
   fake.n_items = n_keys;
+  fake.lazy_items = touched ? 1 : 0;
   hsk_ws w;
   memset(&w, 0, sizeof(w));
   w.it32 = e.it32;
@@ -2076,7 +2075,89 @@ int hsk_keysort_run(const hsk_keysort& e, int64_t n_keys, int64_t n, hipStream_t
   w.btot = e.btot;
   w.bstart = e.bstart;
   w.offsets = e.offsets;
-  return hsk_launch_sort(&fake, w, n, stream);
+  w.touched = touched;
+  w.n_touched = n_touched;
+  return hsk_launch_sort(&fake, w, n, stream, n_dev);
+}
+
+int hsk_keysort_run(const hsk_keysort& e, int64_t n_keys, int64_t n, hipStream_t stream) {
+  return hsk_keysort_run_with(e, n_keys, n, stream, nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// debug / parity: the sort by itself.  hsk_key_sort_plan says which of the three sorts a shape takes (host arithmetic
+// only), hsk_key_sort runs exactly that on the caller's keys -- the same hsk_launch_sort every step and operator
+// goes through.
+// ---------------------------------------------------------------------------------------------
+extern "C" int hsk_key_sort_plan(int64_t n_keys, int64_t n_entries, int want_touched, int64_t out[8]) {
+  const hsk_sort_choice sc = hsk_choose_sort(n_keys, n_entries, want_touched != 0);
+  if (out) {
+    out[0] = sc.kind;
+    out[1] = sc.plan.shift;
+    out[2] = sc.plan.n_buckets;
+    out[3] = sc.plan.ipb;
+    out[4] = sc.plan.epw;
+    out[5] = sc.plan.n_units;
+    out[6] = (int64_t)sc.lds_bytes;
+    out[7] = sc.nbits;
+  }
+  return sc.kind;
+}
+
+struct hsk_keysortw {   // scratch of hsk_key_sort: the key sort's, then the touched list and its count
+  hsk_keysort sort;
+  int *touched, *n_touched;
+  int64_t total;
+};
+
+static hsk_keysortw hsk_keysortw_carve(void* base, int64_t n_keys, int64_t n, bool want_touched) {
+  hsk_keysortw w;
+  w.sort = hsk_keysort_carve(base, n_keys, n);
+  char* p = (char*)base;
+  int64_t off = w.sort.total;
+  auto take = [&](int64_t bytes) {
+    char* r = p ? p + off : nullptr;
+    off += hsk_align_up(bytes, 256);
+    return r;
+  };
+  w.touched = (int*)take(want_touched ? n * 4 : 0);
+  w.n_touched = (int*)take(want_touched ? 4 : 0);
+  w.total = off;
+  return w;
+}
+
+extern "C" int64_t hsk_key_sort_ws_bytes(int64_t n_keys, int64_t n, int want_touched) {
+  if (n <= 0 || hsk_choose_sort(n_keys, n, want_touched != 0).kind == HSK_SORT_UNSUPPORTED) return -1;
+  return hsk_keysortw_carve(nullptr, n_keys, n, want_touched != 0).total;
+}
+
+extern "C" int hsk_key_sort(const int64_t* keys, int64_t n, int64_t n_keys, const int32_t* n_dev, int32_t* perm,
+                            int32_t* offsets, int32_t* touched, int32_t* n_touched, void* ws, int64_t ws_bytes,
+                            int32_t* status, hsk_stream_t stream_) {
+  HSK_REQUIRE(keys && perm && offsets && ws, HSK_ERR_INVALID, "hsk_key_sort: NULL pointer argument");
+  HSK_REQUIRE((touched == nullptr) == (n_touched == nullptr), HSK_ERR_INVALID,
+              "hsk_key_sort: touched and n_touched go together");
+  HSK_REQUIRE(n_keys > 0 && n > 0 && n < 0x7fffffff, HSK_ERR_INVALID, "hsk_key_sort: bad sizes");
+  const bool want_touched = touched != nullptr;
+  const int64_t need = hsk_key_sort_ws_bytes(n_keys, n, want_touched);
+  HSK_REQUIRE(need > 0, HSK_ERR_UNSUPPORTED, "n_keys %lld too large for the item sort (max %lld per device%s)",
+              (long long)n_keys, (long long)hsk_sort_max_keys(want_touched), want_touched ? " with a touched list" : "");
+  HSK_REQUIRE(ws_bytes >= need && ((uintptr_t)ws & 255) == 0, HSK_ERR_INVALID, "hsk_key_sort workspace: %lld bytes needed, %lld given",
+              (long long)need, (long long)ws_bytes);
+  hipStream_t stream = (hipStream_t)stream_;
+  const hsk_keysortw w = hsk_keysortw_carve(ws, n_keys, n, want_touched);
+  k_idx_to_i32<<<(unsigned)hsk_ceil_div(n, 256), 256, 0, stream>>>(keys, (int)n, (int)n_keys, w.sort.it32, status);
+  HSK_LAUNCH_CHECK();
+  int rc = hsk_keysort_run_with(w.sort, n_keys, n, stream, want_touched ? w.touched : nullptr,
+                                want_touched ? w.n_touched : nullptr, n_dev);
+  if (rc) return rc;
+  HSK_HIP(hipMemcpyAsync(perm, w.sort.perm, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+  HSK_HIP(hipMemcpyAsync(offsets, w.sort.offsets, (size_t)(n_keys + 1) * 4, hipMemcpyDeviceToDevice, stream));
+  if (want_touched) {
+    HSK_HIP(hipMemcpyAsync(touched, w.touched, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+    HSK_HIP(hipMemcpyAsync(n_touched, w.n_touched, 4, hipMemcpyDeviceToDevice, stream));
+  }
+  return HSK_OK;
 }
 
 extern "C" int64_t hsk_embedding_backward_ws_bytes(int64_t n_rows, int64_t n) {

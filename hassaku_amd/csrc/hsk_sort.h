@@ -23,8 +23,23 @@
 
 #define HSK_SORT_MAX_BUCKETS 512
 #define HSK_SORT_MAX_UNITS 512
-#define HSK_SORT_MAX_IPB 8192  // items per bucket the level-2 LDS counters can hold (5 x IPB ints <= 160 KB)
+#define HSK_SORT_MAX_IPB 8192  // items per bucket of the level-2 pass at most: its 5 x IPB LDS counters are then 160 KB,
+                               // all a workgroup can have; with the touched list (6 x IPB + 2 ints) half of that fits
 #define HSK_SORT_GROUP 16      // chunks of 64 entries whose loads are issued together
+#define HSK_SORT_LDS_BYTES_MAX 163840   // LDS of one workgroup on gfx950
+
+// dynamic LDS of k_sort_bucket: cnt[4][ipb] + tot[ipb], with the touched list also list[ipb] + 2 counters
+static inline size_t hsk_sort_bucket_lds_bytes(int ipb, bool touched) {
+  return (touched ? (size_t)6 * ipb + 2 : (size_t)5 * ipb) * sizeof(int);
+}
+// the largest bucket (a power of two) whose counters fit: 8192 items, 4096 with the touched list
+static inline int hsk_sort_max_ipb(bool touched) {
+  int ipb = HSK_SORT_MAX_IPB;
+  while (hsk_sort_bucket_lds_bytes(ipb, touched) > HSK_SORT_LDS_BYTES_MAX) ipb >>= 1;
+  return ipb;
+}
+// the most keys any of the sorts takes: 4 194 304, 2 097 152 with the touched list (lazy_items)
+static inline int64_t hsk_sort_max_keys(bool touched) { return (int64_t)HSK_SORT_MAX_BUCKETS * hsk_sort_max_ipb(touched); }
 
 struct hsk_sort_plan {
   int shift;      // bucket = item >> shift
@@ -34,13 +49,13 @@ struct hsk_sort_plan {
   int n_units;    // NU
 };
 
-static inline int hsk_make_sort_plan(int64_t n_items, int64_t n_entries, hsk_sort_plan* p) {
+static inline int hsk_make_sort_plan(int64_t n_items, int64_t n_entries, hsk_sort_plan* p, bool touched = false) {
+  if (n_items > hsk_sort_max_keys(touched)) return -1;
   int shift = 0;
   while (((n_items - 1) >> shift) + 1 > HSK_SORT_MAX_BUCKETS) ++shift;
   p->shift = shift;
   p->ipb = 1 << shift;
   p->n_buckets = (int)(((n_items - 1) >> shift) + 1);
-  if (p->ipb > HSK_SORT_MAX_IPB) return -1;
   int64_t epw = 1024;
   while (hsk_ceil_div(n_entries, epw) > HSK_SORT_MAX_UNITS) epw *= 2;
   p->epw = (int)epw;
@@ -48,10 +63,57 @@ static inline int hsk_make_sort_plan(int64_t n_items, int64_t n_entries, hsk_sor
   return 0;
 }
 
-static inline int64_t hsk_sort_hist_elems(int64_t n_items, int64_t max_entries) {
+static inline int64_t hsk_sort_hist_elems(int64_t n_items, int64_t max_entries, bool touched = false) {
   hsk_sort_plan p;
-  if (hsk_make_sort_plan(n_items, max_entries, &p) != 0) return -1;
+  if (hsk_make_sort_plan(n_items, max_entries, &p, touched) != 0) return -1;
   return (int64_t)p.n_buckets * HSK_SORT_MAX_UNITS;
+}
+
+// k_sort_lds (below): one workgroup, everything in LDS: 3 * n_items + 2 * 8192 + 64 ints
+#define HSK_SORT_LDS_CAP 8192
+static inline size_t hsk_sort_lds_bytes(int64_t n_items) { return ((size_t)3 * n_items + 2 * HSK_SORT_LDS_CAP + 64) * sizeof(int); }
+#define HSK_SORT_LDS_MAX_ITEMS 8000   // 3 x n_items + 16 448 ints <= 160 KB
+// few entries per item on average: the per-item fix-up is what this sort adds to a plain scatter
+static inline bool hsk_sort_lds_fits(int64_t n_items, int64_t n_entries) {
+  return n_entries <= HSK_SORT_LDS_CAP && n_items <= HSK_SORT_LDS_MAX_ITEMS && n_entries <= 4 * n_items;
+}
+
+// Which of the three sorts takes n_entries entries over n_keys keys, and with what: THE dispatch rule (hsk_launch_sort
+// of hsk_fused.hip launches what this says; hsk_key_sort_plan shows it to the tests).  touched: the sort also lists the
+// keys that have entries (lazy_items).
+enum hsk_sort_kind {
+  HSK_SORT_UNSUPPORTED = 0,   // more keys than the level-2 LDS counters hold
+  HSK_SORT_LDS = 1,           // k_sort_lds
+  HSK_SORT_SMALL2 = 2,        // k_sort_small<2>
+  HSK_SORT_SMALL4 = 3,        // k_sort_small<4>
+  HSK_SORT_SMALL8 = 4,        // k_sort_small<8>
+  HSK_SORT_TWO_LEVEL = 5,     // k_sort_hist / k_sort_rowscan / k_sort_scatter / k_sort_bucket
+};
+struct hsk_sort_choice {
+  int kind;
+  hsk_sort_plan plan;   // two-level sort only, zeros otherwise
+  int nbits;            // k_sort_small only: radix bits, keys 0..n_keys (n_keys = padding) fit
+  size_t lds_bytes;     // dynamic LDS of the launch (k_sort_lds, k_sort_bucket; k_sort_small's is static)
+};
+
+static inline hsk_sort_choice hsk_choose_sort(int64_t n_keys, int64_t n_entries, bool touched) {
+  hsk_sort_choice c = {};   // kind = HSK_SORT_UNSUPPORTED
+  if (n_keys <= 0 || n_entries < 0 || n_entries >= 0x7fffffff || n_keys > hsk_sort_max_keys(touched)) return c;
+  if (hsk_sort_lds_fits(n_keys, n_entries)) {
+    c.kind = HSK_SORT_LDS;
+    c.lds_bytes = hsk_sort_lds_bytes(n_keys);
+    return c;
+  }
+  if (n_entries <= 1024 * 8) {
+    c.kind = n_entries <= 1024 * 2 ? HSK_SORT_SMALL2 : n_entries <= 1024 * 4 ? HSK_SORT_SMALL4 : HSK_SORT_SMALL8;
+    c.nbits = 1;
+    while ((1ll << c.nbits) <= (long long)n_keys) ++c.nbits;
+    return c;
+  }
+  if (hsk_make_sort_plan(n_keys, n_entries, &c.plan, touched) != 0) return c;
+  c.kind = HSK_SORT_TWO_LEVEL;
+  c.lds_bytes = hsk_sort_bucket_lds_bytes(c.plan.ipb, touched);
+  return c;
 }
 
 #if defined(__HIPCC__)
@@ -254,7 +316,7 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const int* __restrict__ it
   hsk_sort_scatter_body(it32, hsk_sort_count(n_entries, n_dev), p, hist, btot, perm1, bstart, (int)blockIdx.x, lds);
 }
 
-// lds: (5 * ipb + 2) ints, + ipb with `touched`
+// lds: 5 * ipb ints, 6 * ipb + 2 with `touched` (hsk_sort_bucket_lds_bytes)
 __device__ __forceinline__ void hsk_sort_bucket_body(const int2* __restrict__ perm1, int n_entries, int n_items,
                                                      const hsk_sort_plan& p, const int* __restrict__ bstart,
                                                      int* __restrict__ perm, int* __restrict__ offsets,
@@ -364,7 +426,8 @@ __global__ __launch_bounds__(256) void k_sort_bucket(const int2* __restrict__ pe
 
 // One phase of the two-level sort as extra workgroups of another launch (the in-launch preparation pipeline of
 // hsk_fused.hip): which phase is said by where the struct sits (hsk_ride_fwd / hsk_ride_item).
-#define HSK_PIPE_MAX_IPB 128   // items per bucket the riding bucket phase holds counters for (5 * ipb + 2 ints of LDS)
+#define HSK_PIPE_MAX_IPB 128   // items per bucket the riding bucket phase holds counters for: 5 * ipb ints of LDS
+                               // (hsk_sort_bucket_lds_bytes without the touched list; a riding sort never has one)
 struct hsk_ride_sort {
   int n_blocks;   // workgroups of this phase in the launch (0: none)
   const int* it32;
@@ -442,15 +505,8 @@ __global__ __launch_bounds__(1024) void k_sort_small(const int* __restrict__ it3
 // ascending entry order: lists of <= 8 entries by their own thread (registers, a fixed compare-exchange network),
 // longer ones by a wave (rank = number of smaller entries, counted from LDS).  The result is the stable sort by item,
 // bit for bit what the other two sorts produce.  LDS: 3 * n_items + 2 * 8192 + 64 ints (the second 8192 holds the
-// work list of long items; sized for the worst case).
+// work list of long items; sized for the worst case: hsk_sort_lds_bytes / hsk_sort_lds_fits above).
 // ---------------------------------------------------------------------------------------------
-#define HSK_SORT_LDS_CAP 8192
-static inline size_t hsk_sort_lds_bytes(int64_t n_items) { return ((size_t)3 * n_items + 2 * HSK_SORT_LDS_CAP + 64) * sizeof(int); }
-#define HSK_SORT_LDS_MAX_ITEMS 8000   // 3 x n_items + 16 448 ints <= 160 KB
-// few entries per item on average: the per-item fix-up is what this sort adds to a plain scatter
-static inline bool hsk_sort_lds_fits(int64_t n_items, int64_t n_entries) {
-  return n_entries <= HSK_SORT_LDS_CAP && n_items <= HSK_SORT_LDS_MAX_ITEMS && n_entries <= 4 * n_items;
-}
 
 __device__ __forceinline__ void hsk_cswap(int& a, int& b) {
   const int lo = min(a, b), hi = max(a, b);

@@ -228,6 +228,52 @@ def embedding(table: torch.Tensor, idx: torch.Tensor, status=None) -> torch.Tens
     return _Embedding.apply(table, idx.contiguous(), status)
 
 
+SORT_KINDS = ('unsupported', 'lds', 'small2', 'small4', 'small8', 'two_level')   # hsk_key_sort_plan's return value
+
+
+def key_sort_plan(n_keys: int, n_entries: int, touched: bool = False) -> dict:
+    """Which of the three sorts of csrc/hsk_sort.h `n_entries` entries over `n_keys` keys take, and with what (debug /
+    parity; host arithmetic, no device): {'kind': one of SORT_KINDS, 'shift', 'n_buckets', 'ipb', 'epw', 'n_units' (the
+    two-level plan, else 0), 'lds_bytes' (dynamic LDS of the launch), 'nbits' (radix bits of the block radix sort)}."""
+    out = (ctypes.c_int64 * 8)()
+    kind = _lib.load().hsk_key_sort_plan(int(n_keys), int(n_entries), int(bool(touched)), out)
+    plan = dict(zip(('kind', 'shift', 'n_buckets', 'ipb', 'epw', 'n_units', 'lds_bytes', 'nbits'), (int(v) for v in out)))
+    plan['kind'] = SORT_KINDS[kind]
+    return plan
+
+
+def key_sort(keys: torch.Tensor, n_keys: int, touched: bool = False, n_valid=None):
+    """The stable sort of positions by key, as the step and the operators' backward passes run it (debug / parity).
+    keys int64 [n] in [0, n_keys) -> (perm int32 [n], offsets int32 [n_keys + 1]), with touched=True also (touched
+    int32 [n], n_touched int32 [1]): the keys that have entries, in any order.  n_valid (int, or device int32 [1]):
+    only the first n_valid positions are entries -- perm is then defined up to offsets[n_keys] == n_valid."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(keys, torch.int64, 'keys')
+    if n_valid is not None and not torch.is_tensor(n_valid):   # a host number: the count still reaches the sort on the device
+        n_valid = torch.tensor([int(n_valid)], dtype=torch.int32, device=keys.device)
+    _chk(n_valid, torch.int32, 'n_valid', (1,), optional=True)
+    n = keys.numel()
+    if keys.dim() != 1 or n < 1 or n_keys < 1:
+        raise ValueError(f'keys {tuple(keys.shape)} / n_keys {n_keys}: expected [n >= 1] and n_keys >= 1')
+    nbytes = lib.hsk_key_sort_ws_bytes(n_keys, n, int(bool(touched)))
+    if nbytes <= 0:
+        raise ValueError(f'n_keys {n_keys} too large for the item sort' + (' with a touched list' if touched else ''))
+    dev_ = keys.device
+    # the sort leaves its results in the workspace: poisoned (0xA5A5A5A5 is no position, offset or key), so that a word
+    # a kernel fails to write shows, whatever an earlier call of the same shape left in the allocator's block
+    ws = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device=dev_)
+    perm = torch.full((n,), -1, dtype=torch.int32, device=dev_)
+    offsets = torch.full((n_keys + 1,), -1, dtype=torch.int32, device=dev_)
+    tl = torch.full((n,), -1, dtype=torch.int32, device=dev_) if touched else None
+    tn = torch.full((1,), -1, dtype=torch.int32, device=dev_) if touched else None
+    status = new_status(dev_)
+    _lib.check(lib.hsk_key_sort(_p(keys), n, n_keys, _p(n_valid), _p(perm), _p(offsets), _p(tl), _p(tn), _p(ws), nbytes,
+                                _p(status), _stream()), 'hsk_key_sort')
+    raise_on_status(status, 'key_sort')
+    return (perm, offsets, tl, tn) if touched else (perm, offsets)
+
+
 SPARSE_ROWS_MAX_DIM = {0: 2048, 2: 1024, 1: 512, 3: 512}   # dim % 4 -> widest row hsk_dispatch_dim serves: 64 V 8
 
 

@@ -426,6 +426,27 @@ int64_t hsk_bprmf_batch_columns(const hsk_bprmf_state* st, int64_t batch, int64_
 int hsk_bprmf_last_sort(const hsk_bprmf_state* st, int64_t n_entries, int32_t* perm_out, int32_t* offsets_out,
                         hsk_stream_t stream);
 
+/* The sort by itself (debug / parity), as every step, hsk_embedding_backward and hsk_sparse_rows_sum_backward run it.
+ *   hsk_key_sort_plan  which sort n_entries entries over n_keys keys take -- host arithmetic only, no device needed.
+ *                      Returns (and stores in out[0]) 0 unsupported (too many keys), 1 k_sort_lds, 2 / 3 / 4 k_sort_small
+ *                      with 2 / 4 / 8 entries per thread, 5 the two-level sort; out[1..5] = shift, n_buckets, ipb, epw,
+ *                      n_units of the two-level plan (0 otherwise); out[6] = bytes of dynamic LDS the launch asks for;
+ *                      out[7] = radix bits of k_sort_small (0 otherwise).  want_touched: as a state with lazy_items sorts,
+ *                      listing the keys that have entries -- the level-2 counters then hold half as many keys:
+ *                      n_keys <= 2 097 152 instead of 4 194 304.
+ *   hsk_key_sort       keys int64 [n] (device) in [0, n_keys) -> perm int32 [n] = the positions grouped by key, ascending
+ *                      position inside a key (the stable sort), offsets int32 [n_keys + 1] = where each key's group
+ *                      starts.  touched int32 [n] + n_touched int32 [1] (both or neither, device): the keys that have
+ *                      entries, in any order, and how many.  n_dev (optional, device int32): only the first
+ *                      min(n, *n_dev) positions are entries; offsets[n_keys] is that count and perm is written up to it.
+ *                      A key outside [0, n_keys) sets HSK_STATUS_BAD_INDEX and counts as key 0.  ws: hsk_key_sort_ws_bytes
+ *                      (-1: unsupported), 256-byte aligned.
+ * (No reference counterpart: autograd's scatter-add has no index to show.) */
+int hsk_key_sort_plan(int64_t n_keys, int64_t n_entries, int want_touched, int64_t out[8]);
+int64_t hsk_key_sort_ws_bytes(int64_t n_keys, int64_t n, int want_touched);
+int hsk_key_sort(const int64_t* keys, int64_t n, int64_t n_keys, const int32_t* n_dev, int32_t* perm, int32_t* offsets,
+                 int32_t* touched, int32_t* n_touched, void* ws, int64_t ws_bytes, int32_t* status, hsk_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Multi-GPU fused step: one process per GPU; replaces nn.DataParallel (train/trainer.py:38-41).
  *

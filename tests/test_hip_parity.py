@@ -320,9 +320,12 @@ def test_closing_sweep_is_bitwise_the_dense_sweep_over_row_shapes(ops, D, opt):
 @pytest.mark.parametrize('opt', ['adamw', 'adagrad'])
 def test_lazy_item_adamw_is_bitwise_the_dense_update(ops, opt):
     """lazy_items: item rows outside the batch keep their zero-gradient steps until they are next touched or flushed --
-    bit-identical to updating every item row every step (150 steps: across the flush at 64 and 128), with the two-level
-    sort (I=3000 items, 48 x 10 entries: most rows untouched) and with the single-workgroup sort."""
-    for kw in (dict(U=300, I=3000, D=64, B=48, N=9), dict(U=120, I=900, D=32, B=1000, N=9)):
+    bit-identical to updating every item row every step (150 steps: across the flush at 64 and 128), with the touched
+    list of each of the three sorts: k_sort_lds (I=3000 items, 48 x 10 entries: most rows untouched), the two-level sort
+    (I=900, 1000 x 10 entries) and the block radix sort (I=40, 100 x 12 entries: 30 per item, too dense for k_sort_lds)."""
+    for sort, kw in (('lds', dict(U=300, I=3000, D=64, B=48, N=9)), ('two_level', dict(U=120, I=900, D=32, B=1000, N=9)),
+                     ('small2', dict(U=300, I=40, D=32, B=100, N=11))):
+        assert ops.key_sort_plan(kw['I'], kw['B'] * (kw['N'] + 1), touched=True)['kind'] == sort
         dense, l0 = _run_random_steps(ops, 150, lazy=True, lazy_items=False, optimizer=opt, **kw)
         lazy, l1 = _run_random_steps(ops, 150, lazy=True, lazy_items=True, optimizer=opt, **kw)
         assert l0 == l1
@@ -642,18 +645,22 @@ def test_in_launch_pipeline_equals_side_stream_prefetch(ops, lazy, shape):
 
 
 @pytest.mark.parametrize('shape', [
-    # (n_users, n_items, D, B, K, popular): which of the item sorts the step picks
-    (300, 3706, 32, 128, 51, False),    # k_sort_lds: <= 8192 entries, <= 4 per item on average (BASELINE configs[1] shape)
-    (300, 1682, 32, 128, 2, False),     # k_sort_lds, 256 entries (BASELINE configs[0] shape)
-    (300, 40, 32, 100, 12, False),      # k_sort_lds is not eligible (30 entries per item): block radix sort
-    (300, 2000, 32, 64, 101, True),     # k_sort_lds with popular items: lists far longer than 8 entries (wave rank pass)
-    (300, 5000, 32, 1024, 33, False),   # > 8192 entries: the four-kernel two-level sort
-    (300, 5000, 32, 1024, 33, True),    # ... with lists of thousands of entries
-    (300, 6000, 256, 2048, 17, True),   # item-partitioned forward (P = 2): rows of K + P - 1 columns
+    # (n_users, n_items, D, B, K, popular, sort): which of the item sorts the step picks (hip_ops.key_sort_plan's name)
+    (300, 3706, 32, 128, 51, False, 'lds'),     # k_sort_lds: <= 8192 entries, <= 4 per item on average (BASELINE configs[1] shape)
+    (300, 1682, 32, 128, 2, False, 'lds'),      # k_sort_lds, 256 entries (BASELINE configs[0] shape)
+    (300, 40, 32, 100, 12, False, 'small2'),    # k_sort_lds is not eligible (30 entries per item): block radix sort
+    (300, 2000, 32, 64, 101, True, 'lds'),      # k_sort_lds with popular items: lists far longer than 8 entries (wave rank pass)
+    (300, 5000, 32, 1024, 33, False, 'two_level'),   # > 8192 entries: the four-kernel two-level sort
+    (300, 5000, 32, 1024, 33, True, 'two_level'),    # ... with lists of thousands of entries
+    (300, 6000, 256, 2048, 17, True, 'two_level'),   # item-partitioned forward (P = 2): rows of K + P - 1 columns
+    (300, 500, 32, 128, 16, False, 'small2'),   # 2048 entries: k_sort_small<2> with every thread full (no padding key)
+    (300, 1000, 32, 128, 32, False, 'small4'),  # 4096 entries: k_sort_small<4>, no padding key
+    (300, 2047, 32, 128, 64, False, 'small8'),  # 8192 entries: k_sort_small<8>, no padding key
+    (300, 8000, 32, 128, 64, False, 'lds'),     # k_sort_lds at its largest: 8000 items, 8192 entries, 161 792 B of LDS
 ])
 def test_item_sort_is_the_stable_sort_by_item(ops, shape):
     """perm / offsets of the step's batch == numpy's stable argsort of the item ids, whichever kernel built them."""
-    n_users, n_items, D, B, K, popular = shape
+    n_users, n_items, D, B, K, popular, sort = shape
     rng = np.random.RandomState(11)
     P = {'user_emb': (rng.randn(n_users, D) * 0.05).astype(np.float32),
          'item_emb': (rng.randn(n_items, D) * 0.05).astype(np.float32)}
@@ -669,6 +676,7 @@ def test_item_sort_is_the_stable_sort_by_item(ops, shape):
         assert cols == K + 1
     else:
         assert cols == K
+    assert ops.key_sort_plan(n_items, B * cols)['kind'] == sort
     # partitioned rows: the positive, cols - K columns that are no entries (the sort skips them), the negatives
     i = np.concatenate([i[:, :1], np.full((B, cols - K), -1, dtype=np.int64), i[:, 1:]], axis=1)
     flat = i.reshape(-1)
