@@ -164,6 +164,9 @@ SIGNATURES = {
     'hsk_topk_merge': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     'hsk_rank_metrics': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                  POINTER(c_int32), c_int32, c_void_p, c_void_p]),
+    'hsk_calibration_metrics': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_int64,
+                                        c_int64, c_void_p, c_int64, c_int64, c_double, POINTER(c_int32), c_int32,
+                                        c_void_p, c_void_p, c_void_p]),
     'hsk_knn_pack_dims': (c_int, [c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     'hsk_knn_pack_i8': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     'hsk_knn_gram_i8': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p]),

@@ -39,6 +39,12 @@ void hsk_set_error(const char* fmt, ...);
     }                                                                                      \
   } while (0)
 
+// the cut-offs of one metrics launch (hsk_rank_metrics, hsk_calibration_metrics), in the caller's order
+struct hsk_ks {
+  int k[HSK_MAX_KS];
+  int n;
+};
+
 static inline int64_t hsk_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t hsk_align_up(int64_t a, int64_t b) { return hsk_ceil_div(a, b) * b; }
 

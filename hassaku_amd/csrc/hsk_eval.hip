@@ -1174,12 +1174,6 @@ __global__ __launch_bounds__(256) void k_topk_merge(const float* __restrict__ va
 // =============================================================================================
 // rank metrics: one wave per evaluated user
 // =============================================================================================
-#define HSK_MAX_KS 8
-struct hsk_ks {
-  int k[HSK_MAX_KS];
-  int n;
-};
-
 __global__ __launch_bounds__(256) void k_rank_metrics(const int32_t* __restrict__ topk, int n_rows, int k_max,
                                                       const int64_t* __restrict__ u_idx, int n_users,
                                                       const int64_t* __restrict__ indptr,

@@ -703,6 +703,11 @@ def evaluate_item_sharded(comm: Comm, sharded, dataset, evaluator, chunk: Option
     are all-reduced once at the end.  The candidate exchange of a chunk runs under the scoring of the next one.
     `sharded` is a ShardedBprMf or a TableShards; `dataset` a FullEvalDataset (its CSRs are global); `evaluator`
     supplies K_VALUES and the user groups."""
+    from hassaku_amd.eval.eval import FullEvaluatorCalibrationDecorator
+    if isinstance(evaluator, FullEvaluatorCalibrationDecorator):
+        # the sums below are this function's own: a decorator's metrics would be dropped without a word
+        raise ValueError('calibration metrics (FullEvaluatorCalibrationDecorator) run in single-process evaluation only; '
+                         'item-sharded evaluation takes a plain FullEvaluator')
     sharded.flush()
     W, r = comm.world, comm.rank
     dev = sharded.device

@@ -8,6 +8,9 @@ the ground-truth CSR), then accumulates per-group sums exactly as FullEvaluator 
 (ItemKNN / UserKNN, EASE, P3alpha, SVD) scores chunks of users into float64 rows on the device (its `score_rows`,
 excluded items -inf), then hsk_knn_topk_rows and hsk_rank_metrics (eval/eval.py:222-236 there: float64 scores, topk(100)).  Any other
 `RecommenderAlgorithm` goes through the generic dense path (predict -> mask -> eval_batch).
+
+`FullEvaluatorCalibrationDecorator` (eval/eval.py:121-208) adds the calibration metrics to any of these paths: the
+ranked ones hand it the ids they already hold (`eval_topk` -> hsk_calibration_metrics), the dense ones its `eval_batch`.
 """
 from collections import defaultdict
 from typing import Optional
@@ -18,7 +21,8 @@ import torch
 from hassaku_amd import hip_ops
 from hassaku_amd.algorithms.base_classes import (RecommenderAlgorithm, SGDBasedRecommenderAlgorithm,
                                                   SparseMatrixBasedRecommenderAlgorithm)
-from hassaku_amd.eval.metrics import ndcg_at_k_batch, precision_at_k_batch, recall_at_k_batch
+from hassaku_amd.eval.metrics import (hellinger_distance, jensen_shannon_distance, kl_divergence, ndcg_at_k_batch,
+                                      precision_at_k_batch, recall_at_k_batch)
 from hassaku_amd.utilities.utils import log_info_results
 
 METRIC_NAMES = ('precision', 'recall', 'ndcg')
@@ -53,12 +57,14 @@ class FullEvaluator:
             sel += [(gi, g == gi) for gi in range(self.n_groups)]
         return sel
 
-    def _accumulate(self, u_idxs: torch.Tensor, per_user: dict):
+    def _accumulate(self, u_idxs: torch.Tensor, per_user: dict, count_users: bool = True):
         """per_user: metric name -> tensor [batch].  Sums and group sizes stay on the device (fp64): the host reads
-        them once, in get_results() -- not 12 x (1 + n_groups) times per batch."""
+        them once, in get_results() -- not 12 x (1 + n_groups) times per batch.  count_users = False adds further
+        metrics of a batch whose users are counted already (the calibration decorators)."""
         for gi, rows in self._groups_of(u_idxs):
-            n = u_idxs.shape[0] if rows is None else rows.sum()
-            self.n_entries[gi] = self.n_entries[gi] + n
+            if count_users:
+                n = u_idxs.shape[0] if rows is None else rows.sum()
+                self.n_entries[gi] = self.n_entries[gi] + n
             for name, vals in per_user.items():
                 v = vals if rows is None else vals[rows]
                 if self.aggr_by_group:
@@ -85,6 +91,9 @@ class FullEvaluator:
         per_user = {f'{name}@{k}': metrics[:, t, j] for t, k in enumerate(ks) for j, name in enumerate(METRIC_NAMES)}
         self._accumulate(u_idxs, per_user)
 
+    def eval_topk(self, u_idxs: torch.Tensor, ids: torch.Tensor):
+        """Ranked entry of the decorators: ids [B, k] of the batch, best first.  Nothing here needs them."""
+
     def get_results(self):
         out = {}
         for gi, metrics in self.group_metrics.items():
@@ -96,6 +105,103 @@ class FullEvaluator:
                     out[prefix + name] = torch.cat(acc).cpu().numpy()
         self._reset_internal_dict()
         return out
+
+
+CALIBRATION_METRIC_NAMES = ('hellinger_distance', 'jensen_shannon_distance', 'kl_divergence')
+
+
+class FullEvaluatorCalibrationDecorator(FullEvaluator):
+    """Adds calibration metrics to the evaluator it wraps (eval/eval.py:121-208): per user and cut-off, the distance
+    between the user's train distribution over bins (tags, popularity buckets) and the smoothed distribution of the
+    recommended list, `{prefix}_{hellinger_distance|jensen_shannon_distance|kl_divergence}@{k}`.  Sums, groups and
+    results live in the wrapped evaluator; decorators nest (tag around base, pop around tag).
+
+    On the device the ranked ids every evaluation path already holds go to hsk_calibration_metrics (`eval_topk`): no
+    [batch, k, n_bins] gather and no logits are needed.  CPU tensors take the torch functions of eval/metrics.py in
+    the matrices' own dtype."""
+    CALIBRATION_K_VALUES = [5, 10, 50, 100]
+
+    def __init__(self, full_evaluator: FullEvaluator, item_tag_mtx: torch.Tensor, user_tag_mtx: torch.Tensor,
+                 metric_name_prefix: str = 'tag', beta_smoothening: float = .01):
+        """item_tag_mtx [n_items, n_bins]: row i = distribution of item i over the bins; user_tag_mtx [n_users, n_bins]:
+        row u = distribution of user u's train items; beta_smoothening: Eq. 5 of Steck's Calibrated Recommendations."""
+        assert 0 <= beta_smoothening <= 1, 'Beta value out of bounds'
+        self.full_evaluator = full_evaluator
+        self.item_tag_mtx = item_tag_mtx
+        self.user_tag_mtx = user_tag_mtx
+        self.metric_name_prefix = metric_name_prefix
+        self.beta_smoothening = beta_smoothening
+        self._on_device = {}    # device -> (item matrix, fp64 user matrix, status word): moved once, not per batch
+
+    @property
+    def K_VALUES(self):
+        return self.full_evaluator.K_VALUES
+
+    def _reset_internal_dict(self):
+        self.full_evaluator._reset_internal_dict()
+
+    def _accumulate(self, u_idxs: torch.Tensor, per_user: dict, count_users: bool = True):
+        self.full_evaluator._accumulate(u_idxs, per_user, count_users)
+
+    def get_n_groups(self):
+        return self.full_evaluator.get_n_groups()
+
+    def get_user_to_user_group(self):
+        return self.full_evaluator.get_user_to_user_group()
+
+    def get_results(self):
+        for _item, _user, status in self._on_device.values():
+            hip_ops.raise_on_status(status, f'{self.metric_name_prefix} calibration')
+        return self.full_evaluator.get_results()
+
+    def _device_matrices(self, device):
+        key = str(device)
+        if key not in self._on_device:
+            item = self.item_tag_mtx.to(device)
+            if item.dtype not in (torch.float32, torch.float64):
+                item = item.double()
+            self._on_device[key] = (item.contiguous(), self.user_tag_mtx.to(device, torch.float64).contiguous(),
+                                    hip_ops.new_status(device))
+        return self._on_device[key]
+
+    def _calibration(self, u_idxs: torch.Tensor, ids: torch.Tensor):
+        ks = sorted(self.CALIBRATION_K_VALUES, reverse=True)
+        if ids.shape[1] < ks[0]:
+            raise ValueError(f'calibration needs the {ks[0]} best items per user (CALIBRATION_K_VALUES), got {ids.shape[1]}')
+        ids = ids[:, :ks[0]]
+        names = [f'{self.metric_name_prefix}_{name}' for name in CALIBRATION_METRIC_NAMES]
+        if ids.is_cuda:
+            item, user, status = self._device_matrices(ids.device)
+            met = hip_ops.calibration_metrics(ids.to(torch.int32).contiguous(), u_idxs.to(torch.int64), item, user,
+                                              self.beta_smoothening, ks, status=status)
+            per_user = {f'{name}@{k}': met[:, t, j] for t, k in enumerate(ks) for j, name in enumerate(names)}
+        else:
+            beta = self.beta_smoothening
+            p = self.user_tag_mtx[u_idxs.to(torch.int64)]
+            per_user = {}
+            for k in ks:
+                q = self.item_tag_mtx[ids[:, :k].to(torch.int64)].sum(1)     # rows of the k best items, [batch, n_bins]
+                q /= k
+                q = beta * p + (1 - beta) * q
+                for name, fn in zip(names, (hellinger_distance, jensen_shannon_distance, kl_divergence)):
+                    per_user[f'{name}@{k}'] = fn(p, q).detach()              # kl: the train distribution comes first
+        self._accumulate(u_idxs, per_user, count_users=False)   # the wrapped evaluator counted them
+
+    def eval_batch(self, u_idxs: torch.Tensor, logits: torch.Tensor, y_true: torch.Tensor):
+        self.full_evaluator.eval_batch(u_idxs, logits, y_true)
+        k_max = max(self.CALIBRATION_K_VALUES)
+        if logits.is_cuda and logits.dtype == torch.float32:
+            ids = hip_ops.topk_dense(logits.contiguous(), k_max)[1]
+        else:
+            ids = torch.topk(logits, k=k_max).indices
+        self._calibration(u_idxs, ids)
+
+    def eval_ranked(self, u_idxs: torch.Tensor, metrics: torch.Tensor, ks):
+        self.full_evaluator.eval_ranked(u_idxs, metrics, ks)
+
+    def eval_topk(self, u_idxs: torch.Tensor, ids: torch.Tensor):
+        self.full_evaluator.eval_topk(u_idxs, ids)
+        self._calibration(u_idxs, ids)
 
 
 def _hip_mf_eval(alg, dataset, evaluator: FullEvaluator, device, chunk: int):
@@ -113,6 +219,7 @@ def _hip_mf_eval(alg, dataset, evaluator: FullEvaluator, device, chunk: int):
                                          arrays['excl_indices'], status=status)
         met = hip_ops.rank_metrics(ids, u, arrays['label_indptr'], arrays['label_indices'], ks)
         evaluator.eval_ranked(u, met, ks)
+        evaluator.eval_topk(u, ids)
     alg.check_indices()
 
 
@@ -133,6 +240,7 @@ def _hip_sparse_eval(alg, dataset, evaluator: FullEvaluator, device):
         _, ids = hip_ops.knn_topk_rows(scores, k_max)
         met = hip_ops.rank_metrics(ids, u, arrays['label_indptr'], arrays['label_indices'], ks)
         evaluator.eval_ranked(u, met, ks)
+        evaluator.eval_topk(u, ids)
     alg.check_indices()
 
 

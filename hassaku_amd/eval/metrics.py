@@ -46,3 +46,25 @@ def ndcg_at_k_batch(logits, y_true, k: int = 10, aggr_sum: bool = True, idx_topk
     idcg = (ideal * disc).sum(-1)
     out = torch.where(idcg > 0, dcg / idcg.clamp(min=1e-30), torch.zeros_like(dcg)).clamp(max=1.)
     return out.sum() if aggr_sum else out
+
+
+# ---- distances between two discrete distributions over the last axis (eval/metrics.py:108-152) --------------------
+# Calibration (H. Steck, Calibrated Recommendations, RecSys 2018) compares the bin distribution of a recommended list
+# with the one of the user's history.  No guards: an empty bin gives log 0 = -inf and 0 * inf = NaN, as there.  The
+# device evaluator gets the three per user from hsk_calibration_metrics; these serve CPU tensors and the tests.
+def hellinger_distance(p: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """sqrt(.5 sum (sqrt p - sqrt q)^2), shape [*, d] -> [*]; symmetric."""
+    root_gap = p.sqrt() - q.sqrt()
+    return (root_gap.square().sum(-1) * .5).sqrt()
+
+
+def kl_divergence(true_p: torch.Tensor, model_q: torch.Tensor) -> torch.Tensor:
+    """sum p (log p - log q), shape [*, d] -> [*]; the observed distribution comes first."""
+    log_ratio = true_p.log() - model_q.log()
+    return (true_p * log_ratio).sum(-1)
+
+
+def jensen_shannon_distance(p: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """sqrt(.5 (KL(p|m) + KL(q|m))) with m = .5 (p + q), shape [*, d] -> [*]; NaN where either has an empty bin."""
+    mid = (p + q) * .5
+    return ((kl_divergence(p, mid) + kl_divergence(q, mid)) * .5).sqrt()

@@ -5,15 +5,17 @@ ItemKNN / UserKNN on the train CSR and evaluates on the device); wandb is option
 `running_settings.use_wandb` is true).  Unlike the reference's run_test (which evaluates on the CPU because
 it passes no device, experiment_helper.py:116-117), the test split is scored on the HIP device.
 """
+import os
 import typing
 
 from hassaku_amd.algorithms.algorithms_utils import AlgorithmsEnum
 from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm, SparseMatrixBasedRecommenderAlgorithm
 from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
 from hassaku_amd.conf.conf_parser import parse_conf, parse_conf_file, save_yaml
-from hassaku_amd.data.data_utils import DatasetsEnum, get_dataloader
+from hassaku_amd.data.data_utils import (DatasetsEnum, build_user_and_item_pop_matrix, build_user_and_item_tag_matrix,
+                                         get_dataloader)
 from hassaku_amd.data.dataset import TrainRecDataset
-from hassaku_amd.eval.eval import FullEvaluator, evaluate_recommender_algorithm
+from hassaku_amd.eval.eval import FullEvaluator, FullEvaluatorCalibrationDecorator, evaluate_recommender_algorithm
 from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 from hassaku_amd.train.trainer import Trainer
 from hassaku_amd.utilities.utils import reproducible
@@ -123,6 +125,14 @@ def run_test(alg: AlgorithmsEnum, dataset: DatasetsEnum, conf: typing.Union[str,
     model.load_model_from_path(conf['model_path'])
     evaluator = FullEvaluator(aggr_by_group=True, n_groups=test_loader.dataset.n_user_groups,
                               user_to_user_group=test_loader.dataset.user_to_user_group)
+    if conf.get('measure_calibration', False):
+        # tag and popularity calibration of the recommended lists, as the reference's test driver adds them
+        # (sweep_test.py:64-69): tag around the base evaluator, pop around tag
+        dataset_folder = os.path.join(conf['data_path'], conf['dataset'])
+        user_tag_mtx, item_tag_mtx = build_user_and_item_tag_matrix(dataset_folder)
+        user_pop_mtx, item_pop_mtx = build_user_and_item_pop_matrix(dataset_folder)
+        evaluator = FullEvaluatorCalibrationDecorator(evaluator, item_tag_mtx, user_tag_mtx, metric_name_prefix='tag')
+        evaluator = FullEvaluatorCalibrationDecorator(evaluator, item_pop_mtx, user_pop_mtx, metric_name_prefix='pop')
     metrics_values = evaluate_recommender_algorithm(model, test_loader, evaluator, device,
                                                     verbose=conf['running_settings']['batch_verbose'])
     if wandb is not None:

@@ -860,6 +860,40 @@ def rank_metrics(topk_idx: torch.Tensor, u_idx: torch.Tensor, label_indptr: torc
     return out
 
 
+def calibration_metrics(topk_idx: torch.Tensor, u_idx: torch.Tensor, item_mtx: torch.Tensor, user_mtx: torch.Tensor,
+                        beta: float, ks: Sequence[int], status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> [R, len(ks), 3] fp64 (hellinger distance, jensen-shannon distance, kl divergence) per user and cut-off,
+    between user_mtx[u] (fp64 [n_users, n_bins]) and the smoothed mean of the item_mtx rows (fp32 or fp64
+    [n_items, n_bins], rows may be strided) of the first k ranked ids."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(topk_idx, torch.int32, 'topk_idx')
+    _chk(u_idx, torch.int64, 'u_idx')
+    _chk(user_mtx, torch.float64, 'user_mtx')
+    _chk(status, torch.int32, 'status', (1,), optional=True)
+    if item_mtx is None or not item_mtx.is_cuda:
+        raise RuntimeError('item_mtx must live on the HIP device; there is no CPU path')
+    if item_mtx.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'item_mtx must be float32 or float64, got {item_mtx.dtype}')
+    if topk_idx.dim() != 2 or user_mtx.dim() != 2 or item_mtx.dim() != 2:
+        raise ValueError('topk_idx, item_mtx and user_mtx must be 2-D')
+    R, kmax = topk_idx.shape
+    n_items, n_bins = item_mtx.shape
+    if u_idx.shape != (R,):
+        raise ValueError('u_idx / topk_idx row mismatch')
+    if user_mtx.shape[1] != n_bins:
+        raise ValueError(f'user_mtx has {user_mtx.shape[1]} bins, item_mtx {n_bins}')
+    if item_mtx.stride(1) != 1 or item_mtx.stride(0) < n_bins:
+        raise ValueError('item_mtx rows must be contiguous (a leading dimension >= n_bins is allowed)')
+    ks_arr = (ctypes.c_int32 * len(ks))(*[int(x) for x in ks])
+    out = torch.empty((R, len(ks), 3), dtype=torch.float64, device=topk_idx.device)
+    _lib.check(lib.hsk_calibration_metrics(_p(topk_idx), R, kmax, _p(u_idx), _p(item_mtx),
+                                           int(item_mtx.dtype == torch.float64), n_items, n_bins, item_mtx.stride(0),
+                                           _p(user_mtx), user_mtx.shape[0], n_bins, float(beta), ks_arr, len(ks),
+                                           _p(out), _p(status), _stream()), 'hsk_calibration_metrics')
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # shared by the row scorers of the fitted models (knn, ease, p3, svd)
 # ---------------------------------------------------------------------------------------------------

@@ -694,6 +694,7 @@ int hsk_topk_merge(const float* vals, const int32_t* idx, int64_t n_parts, int64
  * out[r, 3*t+0..2] = precision, recall, ndcg at ks[t].  Semantics of eval/metrics.py:4-105
  * (recall and ndcg are 0 for users without ground truth; ndcg clamped to <= 1).
  */
+#define HSK_MAX_KS 8 /* cut-offs per call of hsk_rank_metrics / hsk_calibration_metrics */
 int hsk_rank_metrics(const int32_t* topk_idx, int64_t n_rows, int64_t k_max,
                      const int64_t* u_idx, int64_t n_users,
                      const int64_t* label_indptr, const int32_t* label_indices,
@@ -756,6 +757,27 @@ int hsk_knn_score_rows(const int64_t* users, int64_t n_users, int64_t n_a_rows, 
  * float64 predictions (eval/eval.py:63). */
 int hsk_knn_topk_rows(const double* scores, int64_t rows, int64_t n_cols, int64_t ld, int64_t k, double* out_vals,
                       int32_t* out_idx, hsk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Calibration metrics (FullEvaluatorCalibrationDecorator, eval/eval.py:121-208; eval/metrics.py:108-152)
+ * ------------------------------------------------------------------------------------------ */
+
+/* Per row r and cut-off ks[t] (host array, n_ks <= HSK_MAX_KS, any order), from the ranked ids topk_idx
+ * [n_rows, k_max] (k_max <= HSK_KNN_MAX_K; the output of hsk_mf_eval_topk / hsk_knn_topk_rows / hsk_topk_merge):
+ *   p = user_mtx[u_idx[r], :]                                   fp64 [n_users, n_bins], leading dimension user_ld
+ *   q = beta p + (1 - beta) (sum over rank < k of item_mtx[id_rank, :]) / k
+ *   out[r, t, 0] = sqrt(.5 sum (sqrt p - sqrt q)^2)            Hellinger distance
+ *   out[r, t, 1] = sqrt(.5 (KL(p|m) + KL(q|m))), m = .5 (p+q)  Jensen-Shannon distance
+ *   out[r, t, 2] = sum p (log p - log q)                       KL divergence
+ * all in fp64, the item rows added in rank order.  item_mtx [n_items, n_bins] with leading dimension item_ld is fp32
+ * (item_is_f64 = 0) or fp64 (1).  Nothing is guarded, as in the reference: a q bin of 0 under p > 0 gives kl = +inf and
+ * js = NaN, a NaN user row gives NaN.  An id outside [0, n_items) (the 0x7fffffff pads of hsk_topk_merge) counts as
+ * a zero row and is not read.  A user id outside [0, n_users) sets HSK_STATUS_BAD_INDEX in *status (may be NULL) and
+ * reads row 0. */
+int hsk_calibration_metrics(const int32_t* topk_idx, int64_t n_rows, int64_t k_max, const int64_t* u_idx,
+                            const void* item_mtx, int32_t item_is_f64, int64_t n_items, int64_t n_bins,
+                            int64_t item_ld, const double* user_mtx, int64_t n_users, int64_t user_ld, double beta,
+                            const int32_t* ks, int32_t n_ks, double* out, int32_t* status, hsk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * EASE (algorithms/linear_algs.py:131-176): G = X^T X + int(lam) I, P = G^-1, B = P / (-diag P) with a zero

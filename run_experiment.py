@@ -3,6 +3,7 @@
 (run_experiment.py:8-36 there), so existing invocations keep working:
 
     python run_experiment.py -a mf -d ml1m -c conf.yml [-t train_val|test|train_val_test] [--log LEVEL]
+                             [--measure_calibration]
 
 Launched under `python -m torch.distributed.run --nproc-per-node N ...` it trains with one process per GPU
 (hassaku_amd/dist.py); nothing else changes on the command line.
@@ -13,6 +14,7 @@ import sys
 
 from hassaku_amd import experiment_helper as helper
 from hassaku_amd.algorithms.algorithms_utils import EXPERIMENT_ALGORITHM_NAMES, AlgorithmsEnum
+from hassaku_amd.conf.conf_parser import parse_conf_file
 from hassaku_amd.data.data_utils import DatasetsEnum
 
 RUN_TYPES = {                      # -t value -> what it runs
@@ -38,9 +40,17 @@ def main(argv=None) -> int:
     cli = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     for names, kw in _flags():
         cli.add_argument(*names, type=str, **kw)
+    # the reference's test driver has this as -c / --measure_calibration; -c is the conf path here
+    cli.add_argument('--measure_calibration', action='store_true', default=False,
+                     help='also report tag and popularity calibration metrics on the test split (sets the conf key '
+                          'measure_calibration; needs tag_idxs.csv and item_tag_idxs.csv in the dataset)')
     opts = cli.parse_args(argv)
     logging.basicConfig(level=opts.log)
-    RUN_TYPES[opts.run_type](AlgorithmsEnum[opts.algorithm], DatasetsEnum[opts.dataset], opts.conf_path)
+    conf = opts.conf_path
+    if opts.measure_calibration:
+        conf = parse_conf_file(conf)
+        conf['measure_calibration'] = True
+    RUN_TYPES[opts.run_type](AlgorithmsEnum[opts.algorithm], DatasetsEnum[opts.dataset], conf)
     return 0
 
 
