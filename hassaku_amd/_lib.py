@@ -43,7 +43,7 @@ class HskBprmfState(ctypes.Structure):
         ('flush_every', c_int32), ('ws_sharded', c_int32),
         # library scratch (zero-initialised by ctypes, never written from Python)
         ('frozen_hyper', c_double * 5), ('frozen_opt', c_int32), ('frozen_valid', c_int32),
-        ('timing_now', c_int32), ('reserved3', c_int32),
+        ('timing_now', c_int32), ('item_pair', c_int32),
     ]
 
 

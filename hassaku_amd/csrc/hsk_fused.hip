@@ -736,6 +736,9 @@ static int hsk_periodic_flush(hsk_bprmf_state* st, const hsk_ws& w, hipStream_t 
 // holds 4096 x 1 KB of user rows; measured 72 us against 93 us for whole rows).  Odd D: whole-row kernel.
 // `Urows` / `urow_index`: where the batch's user rows live (the table + u32, or the exchange buffer + slot_of_b).
 // `ua` (optional, APPLY only): the owners' user-row update rides in the same launch (k_item_user), see hsk_item_sliced.h.
+#ifndef HSK_ITEM_PAIR_HOT_BYTES
+#define HSK_ITEM_PAIR_HOT_BYTES (2 << 20)   // half of an XCD's L2
+#endif
 template <int V, int NCH, bool FULL, int R, bool APPLY>
 static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, const float* Urows, const int* urow_index,
                                  int K, const hsk_adamw_consts& c, float* gI_out, float* gIb_out, hipStream_t stream,
@@ -756,7 +759,7 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
   constexpr int VSC = (V == 4) ? 4 : 2;
   const int ipw = 1;
   const int vs = VSC;
-  const int n_sl = (int)hsk_ceil_div(D, 64 * vs);
+  int n_sl = (int)hsk_ceil_div(D, 64 * vs);
   // merged launch at a small batch: whole-row item workgroups (n_slices_pad = 0 tells the kernel), see hsk_item_row_body
   static const int rows_on = getenv("HSK_ITEM_ROWS") ? atoi(getenv("HSK_ITEM_ROWS")) : 1;
   // lazy item AdamW (catalogues far beyond the caches): whole rows as well -- the launch is p / m / v traffic on the
@@ -764,8 +767,25 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
   // slices' L2 affinity buys nothing for a gather that is a tenth of the bytes
   static const int rows_lazy = getenv("HSK_ITEM_ROWS_LAZY") ? atoi(getenv("HSK_ITEM_ROWS_LAZY")) : 1;
   const bool whole_rows = APPLY && ua && rows_on && (n_entries <= 64 * 1024 || (rows_lazy && st->lazy_items)) && !part;
-  const int n_slices_pad = whole_rows ? 0 : (n_sl < 8 && 8 % n_sl == 0) ? n_sl : (int)hsk_align_up(n_sl, 8);
   const bool lazy = APPLY && st->lazy_items;
+  const bool gen = APPLY && st->opt_kind != HSK_OPT_ADAMW;   // APPLY == false never calls the update
+  // the pair form (hsk_item_pair_body: 128-float slices, two entries per load) of the merged launch, AdamW on every
+  // item of V = 4 rows gathered from ucur (by batch position, 32-bit offsets): when the 256-float slices' hot set, batch
+  // x min(D, 256) floats of user rows per XCD, is more than half an L2, and the lists average a full group of loads
+  // (8 entries; the ml10m shape's 39 gain, the lfm2b shape's 3 lose 7 % with the form forced on).  st->item_pair
+  // (1 / -1) and HSK_ITEM_PAIR (1 / 0) force it on / off, the state's field first.
+  static const int pair_env = getenv("HSK_ITEM_PAIR") ? atoi(getenv("HSK_ITEM_PAIR")) : -1;
+  // (partitions exist for whole chunks only -- hsk_part_rule: D = 256, 512, 1024, 2048, so V == 4 && FULL; a forced
+  // st->item_pair on any other partitioned row would find no kernel, so it is not taken there)
+  bool pair = false;
+  if (APPLY && V == 4 && (FULL || !part) && ua && !urow_index && (int64_t)ua->B * D < (1 << 30) && !whole_rows &&
+      !lazy && !gen) {
+    const int64_t hot = (int64_t)ua->B * std::min(D, 256) * 4;
+    pair = st->item_pair ? st->item_pair > 0 : pair_env >= 0 ? pair_env != 0
+                                                              : hot > HSK_ITEM_PAIR_HOT_BYTES && n_entries >= 8 * (int64_t)I;
+  }
+  if (pair) n_sl = (int)hsk_ceil_div(D, 128);
+  const int n_slices_pad = whole_rows ? 0 : (n_sl < 8 && 8 % n_sl == 0) ? n_sl : (int)hsk_align_up(n_sl, 8);
   // lazy item AdamW: only the items with entries (the sort's `touched` list; at most one per entry)
   const int64_t n_list = lazy ? std::min<int64_t>(I, n_entries) : I;
   const unsigned groups = (unsigned)hsk_align_up(hsk_ceil_div(n_list, 4 * ipw), 8);
@@ -773,7 +793,6 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
                             st->v_item_bias, urow_index, w.g_s, w.perm, w.offsets, I, K, D, n_slices_pad, ipw, c,
                             gI_out, gIb_out, w.touched, w.n_touched, w.last_step_i, (int)st->step, w.pend,
                             ua ? ua->desc : nullptr, ua ? ua->rel : 0, w.adam_tab, HSK_ADAM_TAB_LEN, n_part};
-  const bool gen = APPLY && st->opt_kind != HSK_OPT_ADAMW;   // APPLY == false never calls the update
   const unsigned nblk = groups * (whole_rows ? 1 : n_slices_pad);
   if (APPLY && ua) {
     const int dense = ua->n_users > 0;
@@ -787,6 +806,18 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
     const int stride = n_ahead_oct ? item_oct / n_ahead_oct : 0;
     const int nab_big = ahead.coo_user ? (int)hsk_align_up(hsk_ceil_div(ahead.n, 4), 8) : 0;   // large-batch kernel
 
+    if (pair) {
+      if constexpr (APPLY && V == 4) {
+        if (part) {
+          if constexpr (FULL)
+            k_item_user_pair<NCH, FULL, true><<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, stream>>>(
+                ia, *ua, nub, dense, ri ? *ri : hsk_ride_item{});
+        } else {
+          k_item_user_pair<NCH, FULL><<<nblk + (unsigned)nub, 256, 0, stream>>>(ia, *ua, nub, dense);
+        }
+      }
+      return;
+    }
 #define HSK_ITEM_USER(VS, GEN, LZ)                                                                             \
   do {                                                                                                         \
     if (whole_rows)                                                                                            \

@@ -191,6 +191,158 @@ __device__ __forceinline__ void hsk_item_sliced_body(const hsk_item_args& a, int
   }
 }
 
+// ---- the pair form: 128-float slices, two list entries per load ---------------------------------------------------
+// A slice of 256 floats makes an XCD's hot set batch x 1 KB of user rows: the whole 4 MB L2 at B = 4096, shared with
+// the item stream, so a third of the gather misses.  128-float slices halve it.  To keep 16-byte loads with one item
+// per wave, the two halves of a wave load the same 128 floats of two CONSECUTIVE entries of the item's list: lane
+// (h, l) = (lane >> 5, lane & 31) loads floats 4l .. 4l+3 of entry j + h.  v_permlane32_swap_b32 on registers (0, 2) and
+// (1, 3) then leaves every lane with two floats of entry j and the same two floats of entry j + 1: lane (h, l) owns
+// floats 4l + 2h and 4l + 2h + 1 of the slice.  Each owned float sees fmaf(g_j, x_j, acc), then fmaf(g_j+1, x_j+1, acc):
+// the operations, operands and order of hsk_item_sliced_body, so the bits are the same.
+#ifndef HSK_ITEM_PAIR_MLP
+#define HSK_ITEM_PAIR_MLP 4   // load instructions in flight per wave, two entries each
+#endif
+
+// a's upper 32 lanes <-> b's lower 32 lanes
+__device__ __forceinline__ void hsk_half_swap(float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
+// registers (0, 2) and (1, 3) of a 16-byte load; its own inverse
+__device__ __forceinline__ void hsk_pair_swap(hsk_vec<4>& x) {
+  hsk_half_swap(x.v[0], x.v[2]);
+  hsk_half_swap(x.v[1], x.v[3]);
+}
+
+// MLP loads of two entries each, from entry j of a chunk of nr entries (myu, myg: lane e holds entry e's row and weight;
+// myu is 0 beyond the chunk), summed into acc in list order.  Every load is issued and every lane of it reads a valid
+// address, so that no load hangs on a predicate or a branch (with either, the compiler put a vmcnt(0) in front of every
+// load): lanes beyond D read the head of their row (dl = 0) and never store; a half-wave without an entry reads row 0,
+// and what it read is never used.  TAIL: fewer than 2 MLP entries are left; the multiply-adds of the missing ones
+// are skipped by wave-uniform branches.
+template <int MLP, bool TAIL>
+__device__ __forceinline__ void hsk_pair_gather(const float* __restrict__ Uw, int D, unsigned hm, unsigned dl, int myu,
+                                                float myg, int j, int nr, hsk_vec<2>& acc) {
+  hsk_vec<4> val[MLP];
+#pragma unroll
+  for (int r = 0; r < MLP; ++r) {
+    const int e0 = j + 2 * r;
+    const unsigned r0 = (unsigned)hsk_readlane_i(myu, TAIL ? min(e0, 63) : e0) * (unsigned)D;
+    const unsigned r1 = (unsigned)hsk_readlane_i(myu, TAIL ? min(e0 + 1, 63) : e0 + 1) * (unsigned)D;
+    val[r] = hsk_ldg<4>(Uw + (((r0 & ~hm) | (r1 & hm)) + dl));
+  }
+#pragma unroll
+  for (int r = 0; r < MLP; ++r) {
+    const int e0 = j + 2 * r;
+    hsk_pair_swap(val[r]);   // v[0], v[1]: the owned floats of entry e0; v[2], v[3]: of entry e0 + 1
+    if (!TAIL || e0 < nr) {
+      const float g0 = hsk_readlane_f(myg, e0);
+      acc.v[0] = fmaf(g0, val[r].v[0], acc.v[0]);
+      acc.v[1] = fmaf(g0, val[r].v[1], acc.v[1]);
+    }
+    if (!TAIL || e0 + 1 < nr) {
+      const float g1 = hsk_readlane_f(myg, e0 + 1);
+      acc.v[0] = fmaf(g1, val[r].v[2], acc.v[0]);
+      acc.v[1] = fmaf(g1, val[r].v[3], acc.v[1]);
+    }
+  }
+}
+
+// AdamW item pass (APPLY, no GEN, every item) on V = 4 rows; arguments and workgroup numbering of hsk_item_sliced_body
+// with n_slices_pad counted in 128-float slices.
+template <bool PART>
+__device__ __forceinline__ void hsk_item_pair_body(const hsk_item_args& a, int bid) {
+  const float* __restrict__ Uw = a.Uw;
+  float* __restrict__ Iw = a.Iw;
+  float* __restrict__ Ib = a.Ib;
+  float* __restrict__ mI = a.mI;
+  float* __restrict__ vI = a.vI;
+  float* __restrict__ mIb = a.mIb;
+  float* __restrict__ vIb = a.vIb;
+  const float* __restrict__ g_s = a.g_s;
+  const int* __restrict__ perm = a.perm;
+  const int* __restrict__ offsets = a.offsets;
+  const int n_items = a.n_items, K = a.K, D = a.D, n_slices_pad = a.n_slices_pad, items_per_wave = a.items_per_wave;
+  hsk_adamw_consts c = a.c;
+  int step = a.step;
+  hsk_resolve_step(a.desc, a.rel, a.ctab, a.ctab_len, step, c);
+  const int lane = hsk_lane();
+  const int wave = hsk_uniform_i(threadIdx.x >> 6);
+  int slice, group;
+  if (n_slices_pad < 8) {
+    const int xcd = bid & 7, r = bid >> 3;
+    slice = xcd % n_slices_pad;
+    group = r * (8 / n_slices_pad) + xcd / n_slices_pad;
+  } else {
+    slice = bid % n_slices_pad;
+    group = bid / n_slices_pad;
+  }
+  constexpr int SW = 128;
+  constexpr int MLP = HSK_ITEM_PAIR_MLP;
+  const int h = lane >> 5;
+  const int d4 = slice * SW + (lane & 31) * 4;   // the 4 floats this lane loads from a user row
+  const int d2 = d4 + 2 * h;                     // the 2 floats it owns
+  const bool live = d4 < D;                      // D % 4 == 0: a group of 4 is live or not as a whole, in both halves
+  const unsigned dl = live ? (unsigned)d4 : 0u;
+  const unsigned hm = h ? ~0u : 0u;
+  if (slice * SW >= D) return;
+  const int first = (group * 4 + wave) * items_per_wave;
+  for (int t = 0; t < items_per_wave; ++t) {
+    const int i = first + t;
+    if (i >= n_items) return;
+    const int beg = hsk_uniform_i(offsets[i]);
+    const int end = hsk_uniform_i(offsets[i + 1]);
+    // AdamW operands early: their latency hides under the gather
+    float* const prow = Iw + (long long)i * D;
+    float* const mrow = mI + (long long)i * D;
+    float* const vrow = vI + (long long)i * D;
+    // 8 bytes per lane, plain loads and stores: against p and m travelling as one 16-byte access per lane (lower
+    // half-wave p, upper half-wave m, swapped into and out of the owned layout, write-through) this was 0.5-1.0 us per
+    // step faster in all six rounds of MEASUREMENTS "Item pass: the pair form"
+    hsk_vec<2> p = hsk_zero<2>(), m = hsk_zero<2>(), v = hsk_zero<2>();
+    if (live) {
+      p = hsk_ldg_stream<2>(prow + d2);
+      m = hsk_ldg_stream<2>(mrow + d2);
+      v = hsk_ldg_stream<2>(vrow + d2);
+    }
+    hsk_vec<2> acc = hsk_zero<2>();
+    float gb_lane = 0.f;
+    for (int c0 = beg; c0 < end; c0 += 64) {
+      const int nr = min(64, end - c0);
+      int myu = 0;
+      float myg = 0.f;
+      if (lane < nr) {
+        const int e = perm[c0 + lane];
+        const int bpos = e / K;
+        myg = PART ? hsk_entry_weight<true>(a, e, bpos) : g_s[e];
+        myu = bpos;   // the user rows are laid out by batch position (ucur), fewer than 2^30 floats of them
+      }
+      gb_lane += myg;
+      int j = 0;
+      for (; j + 2 * MLP <= nr; j += 2 * MLP) hsk_pair_gather<MLP, false>(Uw, D, hm, dl, myu, myg, j, nr, acc);
+      if (j < nr) hsk_pair_gather<MLP, true>(Uw, D, hm, dl, myu, myg, j, nr, acc);
+    }
+    if (live) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) hsk_adamw_update<false>(p.v[q], m.v[q], v.v[q], acc.v[q], c);
+      hsk_stg<2>(prow + d2, p);
+      hsk_stg<2>(mrow + d2, m);
+      hsk_stg<2>(vrow + d2, v);
+    }
+    if (slice == 0 && Ib) {
+      const float gbias = hsk_wave_sum(gb_lane);
+      if (lane == 0) {
+        float pb = Ib[i], mb = mIb[i], vb = vIb[i];
+        hsk_adamw_update<false>(pb, mb, vb, gbias, c);
+        Ib[i] = pb;
+        mIb[i] = mb;
+        vIb[i] = vb;
+      }
+    }
+  }
+}
+
 // Whole rows, one wave per item -- what a SMALL batch wants: with a few thousand entries everything is cache-resident
 // and the pass is a chain of latencies per wave (offsets -> perm -> g_s -> rows), so the fewer waves the better; the
 // D-slices above multiply them by the number of slices for an L2 affinity that only matters when the chip is full.
@@ -345,6 +497,36 @@ void k_item_user(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks, int
   }
 #endif
   hsk_item_sliced_body<true, VS, GEN, LAZYI, PART>(ia, bid - n_user_blocks - (LAZYI ? n_ahead_blocks : 0));
+}
+
+// k_item_user<4, NCH, FULL, 4, false, false, PART> with the pair form of the item pass (hsk_item_pair_body): AdamW on
+// every item, rows of D % 4 == 0.  A kernel of its own and not a flag of k_item_user, whose instantiations keep the
+// code they had.
+template <int NCH, bool FULL, bool PART = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void k_item_user_pair(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks, int dense_users, hsk_ride_item ri = hsk_ride_item{}) {
+  constexpr int POL_OWNER = hsk_stream_policy(HSK_STREAM_OWNER);
+  int bid = (int)blockIdx.x;
+  if (PART) {   // the riders, as in k_item_user
+    if (bid < ri.n_total) {
+      __shared__ int ride_lds[HSK_SORT_SCATTER_LDS];
+      if (bid < ri.C.n_blocks) {
+        hsk_sort_scatter_body(ri.C.it32, ri.C.n_entries, ri.C.plan, ri.C.hist, ri.C.btot, ri.C.perm1, ri.C.bstart, bid, ride_lds);
+      } else if (bid - ri.C.n_blocks < ri.H.n_blocks) {
+        hsk_sort_hist_body(ri.H.it32, ri.H.n_entries, ri.H.plan, ri.H.hist, bid - ri.C.n_blocks, ride_lds);
+      }
+      return;
+    }
+    bid -= ri.n_total;
+  }
+  if (bid < n_user_blocks) {
+    if (dense_users)
+      hsk_user_update_dense_body<4, NCH, FULL, false, PART, POL_OWNER>(ua, bid);
+    else
+      hsk_user_update_lazy_body<4, NCH, FULL, false, PART, POL_OWNER>(ua, bid);
+    return;
+  }
+  hsk_item_pair_body<PART>(ia, bid - n_user_blocks);
 }
 
 // small batches: whole-row item workgroups, interleaved with the ahead workgroups

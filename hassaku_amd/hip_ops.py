@@ -508,6 +508,8 @@ class BprMfFusedState:
         # steps_sampled() replays its steady-state loop as HIP graphs of this many steps (0: default 64, < 0: never)
         st.graph_chunk = int(graph_chunk)
         st.catchup_apart = 0
+        # form of the large-batch item pass: 0 by the library's rule, 1 / -1 the pair form forced on / off (same bits)
+        st.item_pair = 0
         # steps between the periodic sweeps of the lazily updated tables; 0: from the table / batch sizes
         # (hsk_bprmf_flush_cadence; a speed matter only -- every cadence gives the same bits)
         st.flush_every, st.ws_sharded = int(flush_every), 0

@@ -287,7 +287,10 @@ typedef struct hsk_bprmf_state {
   int32_t frozen_valid;
   /* whether the step being issued is an event-timed one (from timing_every) */
   int32_t timing_now;
-  int32_t reserved3;
+  /* CALLER-OWNED option in the place of a reserved word (the layout is what it was): the form of the large-batch item
+     pass.  0 (default): chosen by the batch's hot set, or by the environment's HSK_ITEM_PAIR = 0 / 1; 1: the pair
+     form (128-float slices, two list entries per load) wherever it exists; -1: never.  Bit-identical results */
+  int32_t item_pair;
 } hsk_bprmf_state;
 
 int64_t hsk_bprmf_workspace_bytes(int64_t n_users, int64_t n_items, int64_t dim,
