@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
   while (true) {
     float gv = 0.f, xv = 0.f;
     auto process = [&](Row(&buf)[R], int j) {
-      hsk_weigh_rows<LOSS>(ur, buf, j, nr, lane, mybias, s0, inv_norm, acc, gsum, gv, xv);
+      hsk_weigh_rows<LOSS, false>(ur, buf, j, nr, lane, mybias, s0, inv_norm, acc, gsum, gv, xv);   // plain quotient: hsk_rows.h
     };
     for (int j = 0; j < nr; j += 2 * R) {
       prefetch(bufB, j + R);
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
   if (LOSS == HSK_LOSS_BPR) {
     gp = gsum;
   } else {
-    gp = (q == 0) ? inv_norm / (1.f + expf(s0)) : 0.f;   // -(sigma(s_0) - 1)/(B*K), once per positive
+    gp = (q == 0) ? hsk_sigmoid_neg_scaled<false>(inv_norm, s0) : 0.f;   // -(sigma(s_0) - 1)/(B*K), once per positive
     if (q == 0 && lane == 0) lsum += (double)hsk_softplus(-s0);
   }
   hsk_row_axpy(acc, -gp, r0);

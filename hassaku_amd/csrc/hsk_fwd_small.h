@@ -119,7 +119,7 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_ugrad_wg(const float* __restric
   if (LOSS == HSK_LOSS_BPR) {
     g0 = -gtot;   // d loss / d s_pos
   } else {
-    g0 = -inv_norm / (1.f + expf(s0));   // (sigma(s_0) - 1)/(B*K)
+    g0 = -hsk_sigmoid_neg_scaled(inv_norm, s0);   // (sigma(s_0) - 1)/(B*K)
     ltot += (double)hsk_softplus(-s0);
   }
   hsk_row_axpy(acc, g0, r0);

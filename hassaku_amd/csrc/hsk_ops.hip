@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_bpr_loss_grad(const float* __restrict__
   for (long long k = 1 + lane; k < K; k += 64) {
     const float x = s0 - row[k];
     lsum += (double)hsk_softplus(-x);
-    const float g = inv_bn / (1.f + expf(x));
+    const float g = hsk_sigmoid_neg_scaled(inv_bn, x);
     gsum += g;
     if (grad) grad[(long long)b * K + k] = g;
   }
@@ -373,20 +373,24 @@ __global__ __launch_bounds__(256) void k_rec_loss_grad(int kind, const float* __
       const float s = row[k];
       const bool pos = (k == 0);
       lsum += (double)hsk_softplus(pos ? -s : s);
-      if (grow) grow[k] = pos ? -inv_norm / (1.f + expf(s)) : inv_norm / (1.f + expf(-s));
+      if (grow) grow[k] = pos ? -hsk_sigmoid_neg_scaled(inv_norm, s) : hsk_sigmoid_neg_scaled(inv_norm, -s);
     }
   } else {  // sampled softmax
     float mx = -INFINITY;
     for (long long k = lane; k < K; k += 64) mx = fmaxf(mx, row[k] + (k == 0 ? 0.f : log_adjust));
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-    float sum = 0.f;
-    for (long long k = lane; k < K; k += 64) sum += expf(row[k] + (k == 0 ? 0.f : log_adjust) - mx);
-    sum = hsk_wave_sum(sum);
+    // the negatives' exponentials are summed on their own: the positive's weight p_0 / B - 1 / B is -(their sum) / (L B),
+    // not a difference of two nearly equal numbers where p_0 -> 1
+    float sneg = 0.f;
+    for (long long k = lane; k < K; k += 64)
+      if (k > 0) sneg += expf(row[k] + log_adjust - mx);
+    sneg = hsk_wave_sum(sneg);
+    const float sum = expf(row[0] - mx) + sneg;
     const float rinv = inv_norm / sum;
     if (grow)
       for (long long k = lane; k < K; k += 64)
-        grow[k] = expf(row[k] + (k == 0 ? 0.f : log_adjust) - mx) * rinv - (k == 0 ? inv_norm : 0.f);
+        grow[k] = (k == 0) ? -sneg * rinv : expf(row[k] + log_adjust - mx) * rinv;
     if (lane == 0) lsum = (double)(-row[0] + mx + logf(sum));
   }
   const double l = hsk_wave_sum_f64(lsum);

@@ -124,6 +124,30 @@ __device__ __forceinline__ float hsk_softplus(float z) {
   return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
 }
 
+// inv * sigma(-x) = inv / (1 + exp(x)): the weight of a BPR / BCE entry.  Past x = 88.72 expf(x) is +inf and the quotient
+// 0, while inv * exp(-x) is still an fp32 subnormal (up to inv * 2^-128: hundreds of steps of 2^-149 at a small batch).
+// TINY: there the weight is taken from expf(-x) instead; wherever expf(x) is finite the bits are those of the quotient.
+// The empty asm keeps the second exponential behind a branch that no lane takes on ordinary scores (left to itself the
+// compiler evaluates both on every call: 17 vector instructions per buffer of rows).  (tests/test_loss_range.py, `wide`)
+// TINY = false is the plain quotient, kept in k_fwd_part alone, whose gather loop has no register to spare
+// (hsk_fwd_part.h) and whose instruction stream this leaves as it was.  It is launched from B >= 2048 and N >= 16 only
+// (hsk_part_rule), so inv <= 2^-15 and an entry past x = 88.72 loses at most inv * 2^-128 <= 2^-143: 0.1 * 2^21 / (B N)
+// steps of 2^-149 of exp_avg -- up to 6.4 steps PER ENTRY at B N = 32 768, under one step from B N = 2.1e5 on.  The
+// 8 + (n - 1) steps tests/test_loss_range.py grants an element of n entries therefore hold for k_fwd_part only where
+// n = 1 or B N >= 2.1e5 (the tested shape, B N = 278 528: 0.75 steps per entry); below that, and for x > 88.72 only,
+// k_fwd_part and the other forwards differ by those few steps of 2^-149.
+template <bool TINY = true>
+__device__ __forceinline__ float hsk_sigmoid_neg_scaled(float inv, float x) {
+  const float e = expf(x);
+  float g = inv / (1.f + e);
+  if (TINY && e == INFINITY) {
+    float nx = -x;
+    asm volatile("" : "+v"(nx));
+    g = inv * expf(nx);
+  }
+  return g;
+}
+
 // Weigh the rows of one buffer (BPR and BCE): buf[0..R) hold entries j .. j+R-1 of a chunk of nr <= 64 entries, lane l
 // of `mybias` holds entry l's item bias.  The score of entry j+r is written into lane j+r of one vector, so x and
 // g = d loss / d s are evaluated ONCE per buffer, lane-parallel, instead of once per row in all 64 lanes (expf, the
@@ -131,7 +155,7 @@ __device__ __forceinline__ float hsk_softplus(float z) {
 // functions and the reduction tree, the operands of the bias add, the order of gsum and of the axpys are what the
 // row-by-row loop had: identical bits.  Lanes outside [j, j+R) n [0, nr) carry garbage through expf and the division;
 // they reach neither gv / xv (the chunk's per-lane g and x, merged here) nor gsum nor acc.
-template <int LOSS, int V, int NCH, int R>
+template <int LOSS, bool TINY = true, int V, int NCH, int R>
 __device__ __forceinline__ void hsk_weigh_rows(const hsk_row<V, NCH>& ur, const hsk_row<V, NCH> (&buf)[R], int j, int nr,
                                                int lane, float mybias, float s0, float inv_norm, hsk_row<V, NCH>& acc,
                                                float& gsum, float& gv, float& xv) {
@@ -145,10 +169,10 @@ __device__ __forceinline__ void hsk_weigh_rows(const hsk_row<V, NCH>& ur, const 
   float x, g;
   if (LOSS == HSK_LOSS_BPR) {
     x = s0 - s;
-    g = inv_norm / (1.f + expf(x));    // sigma(-x)/(B*N) = d loss / d s_neg
+    g = hsk_sigmoid_neg_scaled<TINY>(inv_norm, x);    // sigma(-x)/(B*N) = d loss / d s_neg
   } else {
     x = s;
-    g = inv_norm / (1.f + expf(-s));   // sigma(s)/(B*K), label 0
+    g = hsk_sigmoid_neg_scaled<TINY>(inv_norm, -s);   // sigma(s)/(B*K), label 0
   }
   const bool mine = lane >= j && lane < min(j + R, nr);
   gv = mine ? g : gv;

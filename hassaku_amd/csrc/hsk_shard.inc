@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void k_shard_pos_fix(const float* __restrict__
   float g0;
   if (LOSS == HSK_LOSS_BCE) {
     const float s0 = s0own[b];
-    g0 = -inv_norm / (1.f + expf(s0));
+    g0 = -hsk_sigmoid_neg_scaled(inv_norm, s0);
     if (lane == 0) loss_b[b] += (double)hsk_softplus(-s0);
   } else {
     g0 = -gsum[b];
@@ -435,7 +435,8 @@ __global__ __launch_bounds__(256) void k_shard_ssm_fix(const float* __restrict__
   float M = fmaxf(m_r, s0);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) M = fmaxf(M, __shfl_xor(M, off, HSK_WAVE));
-  const float L = expf(s0 - M) + hsk_wave_sum(l_r * expf(m_r - M));   // (lanes >= world: 0 * exp(-inf) = 0)
+  const float Lneg = hsk_wave_sum(l_r * expf(m_r - M));   // (lanes >= world: 0 * exp(-inf) = 0)
+  const float L = expf(s0 - M) + Lneg;
   const float rinv = inv_norm / L;
   const float m_me = hsk_readlane_f(m_r, rank);
   const float scale = expf(m_me - M) * rinv;     // 0 for a rank without negatives of this positive (m_me = -inf)
@@ -452,7 +453,7 @@ __global__ __launch_bounds__(256) void k_shard_ssm_fix(const float* __restrict__
 #pragma unroll
     for (int q = 0; q < V; ++q) acc.c[cc].v[q] *= scale;
   if (own) {
-    const float g0 = expf(s0 - M) * rinv - inv_norm;
+    const float g0 = -Lneg * rinv;   // p_0 / G - 1 / G without the difference
     hsk_row<V, NCH> r0;
     hsk_row_load<V, NCH, FULL>(r0, Iw + (long long)pl * D, lane, D);
     hsk_row_axpy(acc, g0, r0);

@@ -183,8 +183,10 @@ __global__ __launch_bounds__(256) void k_fwd_ugrad(const float* __restrict__ Uw,
 
   float gsum = 0.f;    // BPR: sum over negatives of sigma(-x)/(B*N)   (wave-uniform)
   double lsum = 0.0;   // per-lane partial of the loss terms
-  float smax = s0, ssum = 1.f;   // SSM: running max and sum of exp(z - smax), z_0 = s_0
-  if (LOSS == HSK_LOSS_SSM) acc = r0;  // exp(z_0 - smax) = 1
+  // SSM: running max (z_0 = s_0 included) and the sum of exp(z - smax) over the NEGATIVES only; acc likewise.  The
+  // positive's weight p_0 / B - 1 / B is taken as -(sum over the negatives) / (L B): no difference of two nearly equal
+  // numbers where p_0 -> 1 (tests/test_loss_range.py)
+  float smax = s0, ssum = 0.f;
 
   for (int kc = 1; kc < K; kc += 64) {
     const int nr = min(64, K - kc);
@@ -250,22 +252,23 @@ __global__ __launch_bounds__(256) void k_fwd_ugrad(const float* __restrict__ Uw,
     g0 = -gsum;                       // d loss / d s_pos = -sum_n sigma(-x_n)/(B*N)
     hsk_row_axpy(acc, g0, r0);
   } else if (LOSS == HSK_LOSS_BCE) {
-    g0 = -inv_norm / (1.f + expf(s0));   // (sigma(s_0) - 1)/(B*K)
+    g0 = -hsk_sigmoid_neg_scaled(inv_norm, s0);   // (sigma(s_0) - 1)/(B*K)
     hsk_row_axpy(acc, g0, r0);
     if (lane == 0) lsum += (double)hsk_softplus(-s0);
   } else {
-    // softmax_k = exp(z_k - smax)/ssum;  d loss/d s_k = (softmax_k - [k==0]) / B
-    const float rinv = inv_norm / ssum;
-    g0 = expf(s0 - smax) * rinv - inv_norm;
+    // softmax_k = exp(z_k - smax)/L, L = exp(s_0 - smax) + ssum;  d loss/d s_k = (softmax_k - [k==0]) / B
+    const float L = expf(s0 - smax) + ssum;
+    const float rinv = inv_norm / L;
+    g0 = -ssum * rinv;
 #pragma unroll
     for (int cc = 0; cc < NCH; ++cc)
 #pragma unroll
-      for (int q = 0; q < V; ++q) acc.c[cc].v[q] = fmaf(acc.c[cc].v[q], rinv, -inv_norm * r0.c[cc].v[q]);
+      for (int q = 0; q < V; ++q) acc.c[cc].v[q] = fmaf(g0, r0.c[cc].v[q], acc.c[cc].v[q] * rinv);
     for (int k = 1 + lane; k < K; k += 64) {   // stored z_k -> gradients (same lanes wrote them)
       const float z = g_s[(long long)b * K + k];
       g_s[(long long)b * K + k] = expf(z - smax) * rinv;
     }
-    if (lane == 0) lsum += (double)(-s0 + smax + logf(ssum));
+    if (lane == 0) lsum += (double)(-s0 + smax + logf(L));
   }
   if (lane == 0) g_s[(long long)b * K] = g0;
   // row-sharded user tables: the gradient row goes straight into its slot of the all-to-all send buffer
