@@ -30,6 +30,9 @@
                            // per buffer need 129 registers (three waves per SIMD); three rows: 114, and the same step time
                            // (188.3 against 188 us, measured in round 3 before the phases rode along)
 #endif
+#ifndef HSK_FWD_OVERLAP_DEFAULT
+#define HSK_FWD_OVERLAP_DEFAULT 1   // the overlapped gather loop of k_fwd_part unless st->fwd_overlap / HSK_FWD_OVERLAP say otherwise
+#endif
 #define HSK_ADAM_TAB_LEN 65536   // per-step (step_size, bc2_sqrt) table for the lazy replay
 #define HSK_FLUSH_NEVER (1 << 30) // cadence of a table whose periodic sweep never pays (an explicit flush still sweeps)
 
@@ -1147,23 +1150,30 @@ static int hsk_run_step(hsk_bprmf_state* st, const hsk_ws& w_all, int set, bool 
         const hsk_part_args pa = {n_part, (int)st->n_items, n_ahead, stride};
         const hsk_ride_fwd rf = (aux && aux->ride_fwd) ? *aux->ride_fwd : hsk_ride_fwd{};   // riding preparation phases
         const unsigned grid = (unsigned)rf.n_total + (unsigned)n_ahead + n_unit;
-#define HSK_LAUNCH_FWD_PART(LK, GEN)                                                                                 \
+        // the overlapped gather loop (hsk_fwd_part.h: OVL) or the loop with a test per row: st->fwd_overlap (1 / -1) and
+        // HSK_FWD_OVERLAP (1 / 0) force it on / off, the state's field first; same bits either way
+        static const int ovl_env = getenv("HSK_FWD_OVERLAP") ? atoi(getenv("HSK_FWD_OVERLAP")) : -1;
+        const bool ovl = st->fwd_overlap ? st->fwd_overlap > 0 : ovl_env >= 0 ? ovl_env != 0 : HSK_FWD_OVERLAP_DEFAULT != 0;
+#define HSK_LAUNCH_FWD_PART_O(LK, GEN, OVL)                                                                         \
   if (capturing)                                                                                                    \
-    hipLaunchKernelGGL((k_fwd_part<V, NCH, FULL, RP, LK, GEN>), dim3(grid), dim3(256), 0, stream,                    \
+    hipLaunchKernelGGL((k_fwd_part<V, NCH, FULL, RP, LK, GEN, OVL>), dim3(grid), dim3(256), 0, stream,               \
                        (const float*)st->user_emb, (const float*)st->item_emb, (const float*)st->item_bias,         \
                        (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D, inv_bn, w.g_s, w.dUb, w.loss_b, lz,  \
                        pa, aa, rf);                                                                                 \
   else                                                                                                              \
-    hipExtLaunchKernelGGL((k_fwd_part<V, NCH, FULL, RP, LK, GEN>), dim3(grid), dim3(256), 0, stream, fwd_beg, fwd_end, \
-                          0, (const float*)st->user_emb, (const float*)st->item_emb, (const float*)st->item_bias,   \
-                          (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D, inv_bn, w.g_s, w.dUb, w.loss_b,  \
-                          lz, pa, aa, rf)
+    hipExtLaunchKernelGGL((k_fwd_part<V, NCH, FULL, RP, LK, GEN, OVL>), dim3(grid), dim3(256), 0, stream, fwd_beg,   \
+                          fwd_end, 0, (const float*)st->user_emb, (const float*)st->item_emb,                        \
+                          (const float*)st->item_bias, (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D,    \
+                          inv_bn, w.g_s, w.dUb, w.loss_b, lz, pa, aa, rf)
+#define HSK_LAUNCH_FWD_PART(LK, GEN)                                                                                 \
+  if (ovl) { HSK_LAUNCH_FWD_PART_O(LK, GEN, true); } else { HSK_LAUNCH_FWD_PART_O(LK, GEN, false); }
         if (st->loss_kind == HSK_LOSS_BCE) {
           if (gen) { HSK_LAUNCH_FWD_PART(HSK_LOSS_BCE, true); } else { HSK_LAUNCH_FWD_PART(HSK_LOSS_BCE, false); }
         } else {
           if (gen) { HSK_LAUNCH_FWD_PART(HSK_LOSS_BPR, true); } else { HSK_LAUNCH_FWD_PART(HSK_LOSS_BPR, false); }
         }
 #undef HSK_LAUNCH_FWD_PART
+#undef HSK_LAUNCH_FWD_PART_O
         return HSK_OK;
       } else {
         hsk_set_error("internal: item-partitioned forward selected for dim %d", D);
@@ -1619,7 +1629,7 @@ __global__ void k_set_desc(hsk_step_desc* d, long long start0, const int64_t* or
 // timing fields may differ between capture and replay (the former is read from the device descriptor).  A caller that
 // changes anything else between two hsk_bprmf_train_steps calls -- an LR schedule through st->lr, parameters rebound
 // after .to(), a new dataset -- gets a fresh capture, exactly as the eager path would pick the new values up.
-static_assert(sizeof(hsk_bprmf_state) == 424, "hsk_bprmf_state has no padding holes: its byte image is a valid key");
+static_assert(sizeof(hsk_bprmf_state) == 432, "hsk_bprmf_state has no padding holes: its byte image is a valid key");
 static hsk_bprmf_state hsk_graph_key(const hsk_bprmf_state* st) {
   hsk_bprmf_state k;
   memcpy(&k, st, sizeof(k));

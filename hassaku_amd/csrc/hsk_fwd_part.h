@@ -73,7 +73,9 @@ __device__ __forceinline__ void hsk_ride_fwd_roles(const hsk_ride_fwd& rf, int b
   if (bid < rf.R.n_blocks) hsk_sort_rowscan_body(rf.R.hist, rf.R.plan, rf.R.btot, bid);
 }
 
-template <int V, int NCH, bool FULL, int R, int LOSS, bool GEN>
+// OVL: the overlapped gather loop (below, at the loop); false: the loop as it was, kept selectable (st->fwd_overlap /
+// HSK_FWD_OVERLAP) so that the two can be compared for equal bits inside one process.
+template <int V, int NCH, bool FULL, int R, int LOSS, bool GEN, bool OVL = false>
 __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, const float* __restrict__ Iw,
                                                   const float* __restrict__ Ib, const int* __restrict__ u32,
                                                   const int* __restrict__ it32, int B, int K /* columns */, int D, float inv_norm,
@@ -165,7 +167,40 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
       if (j + r < nr)
         hsk_row_load<V, NCH, FULL>(buf[r], Iw + (long long)hsk_readlane_i(myidx, j + r) * D, lane, D);
   };
-  prefetch(bufA, 0);
+  // OVL: every load of a buffer is issued, on every path, and reads a valid row -- an entry at or beyond nr names the
+  // chunk's last entry, a row the same gather asks for anyway (the positive's row, i0, which an empty list finds in lane 0,
+  // has often left the L2 by then: 30 MB more fabric reads per launch when the spare loads named it).  With no
+  // branch between a buffer's loads and its first use the wait there is a COUNTED s_waitcnt vmcnt(n) that leaves the
+  // other buffer's loads in flight; behind `if (j + r < nr)` the count depends on the path and the compiler waits for
+  // everything (MEASUREMENTS, "a buffer's loads stay in flight").
+  // pinned (inside the loop): the order of the loop's four phases is held by data dependences, through empty asm
+  // statements that emit no instruction.  In front of the loads, acc and the row indices pass through one: the gather
+  // comes behind everything summed into acc so far, so the buffer it overwrites is dead by then -- no third buffer, no
+  // copies (129 registers and three waves per SIMD otherwise).  Behind the loads and a scheduling barrier, ur does: the
+  // other buffer's first use, and the wait in front of it, come after the loads.
+  auto gather = [&](Row(&buf)[R], int j, bool pinned) {
+    int idx[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) idx[r] = hsk_readlane_i(myidx, min(j + r, max(nr, 1) - 1));
+    if (pinned) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int i = 0; i < V; ++i) asm volatile("" : "+v"(acc.c[c].v[i]));
+#pragma unroll
+      for (int r = 0; r < R; ++r) asm volatile("" : "+s"(idx[r]));
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) hsk_row_load<V, NCH, FULL>(buf[r], Iw + (long long)idx[r] * D, lane, D);
+    if (pinned) {
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int i = 0; i < V; ++i) asm volatile("" : "+v"(ur.c[c].v[i]));
+    }
+  };
+  if constexpr (OVL) gather(bufA, 0, false); else prefetch(bufA, 0);
   float mybias = Ib ? Ib[myidx] : 0.f;
 
   if (lz.mU)
@@ -183,11 +218,34 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
     auto process = [&](Row(&buf)[R], int j) {
       hsk_weigh_rows<LOSS, false>(ur, buf, j, nr, lane, mybias, s0, inv_norm, acc, gsum, gv, xv);   // plain quotient: hsk_rows.h
     };
-    for (int j = 0; j < nr; j += 2 * R) {
-      prefetch(bufB, j + R);
-      process(bufA, j);
-      prefetch(bufA, j + 2 * R);
-      process(bufB, j + R);
+    if constexpr (OVL) {
+      auto process_full = [&](Row(&buf)[R], int j) {
+        hsk_weigh_rows<LOSS, false, true>(ur, buf, j, nr, lane, mybias, s0, inv_norm, acc, gsum, gv, xv);
+      };
+      // main path, straight-line: both buffers full and at least one entry behind them (bufA's next rows: entries past
+      // nr are the valid rows named above, at most R - 1 of them per chunk)
+      int j = 0;
+      for (; j + 2 * R < nr; j += 2 * R) {
+        gather(bufB, j + R, true);
+        process_full(bufA, j);
+        gather(bufA, j + 2 * R, true);
+        process_full(bufB, j + R);
+      }
+      // peeled tail, 0 .. 2R entries in bufA (on its way) and bufB (not asked for yet); a buffer nobody needs is not loaded
+      if (j + R < nr) {
+        gather(bufB, j + R, true);
+        process_full(bufA, j);
+        process(bufB, j + R);
+      } else {
+        process(bufA, j);
+      }
+    } else {
+      for (int j = 0; j < nr; j += 2 * R) {
+        prefetch(bufB, j + R);
+        process(bufA, j);
+        prefetch(bufA, j + 2 * R);
+        process(bufB, j + R);
+      }
     }
     if (lane < nr) {
       g_s[(long long)b * K + mycol] = gv;
@@ -198,7 +256,7 @@ __global__ __launch_bounds__(256) void k_fwd_part(const float* __restrict__ Uw, 
     nr = min(64, n_mine - kc);
     myidx = (lane < nr) ? lst_id[wave][kc + lane] : i0;
     mycol = (lane < nr) ? lst_col[wave][kc + lane] : 0;
-    prefetch(bufA, 0);
+    if constexpr (OVL) gather(bufA, 0, false); else prefetch(bufA, 0);
     mybias = Ib ? Ib[myidx] : 0.f;
   }
   float gp;   // this unit's share of -d loss/d s_0

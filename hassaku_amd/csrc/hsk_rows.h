@@ -155,16 +155,18 @@ __device__ __forceinline__ float hsk_sigmoid_neg_scaled(float inv, float x) {
 // functions and the reduction tree, the operands of the bias add, the order of gsum and of the axpys are what the
 // row-by-row loop had: identical bits.  Lanes outside [j, j+R) n [0, nr) carry garbage through expf and the division;
 // they reach neither gv / xv (the chunk's per-lane g and x, merged here) nor gsum nor acc.
-template <int LOSS, bool TINY = true, int V, int NCH, int R>
+// FULL_BUF: the caller vouches for j + R <= nr -- no test per row, no clamp of `mine`: one straight-line block, which the
+// overlapped gather loop (hsk_fwd_part.h) needs around its loads; the same operations on the same operands otherwise.
+template <int LOSS, bool TINY = true, bool FULL_BUF = false, int V, int NCH, int R>
 __device__ __forceinline__ void hsk_weigh_rows(const hsk_row<V, NCH>& ur, const hsk_row<V, NCH> (&buf)[R], int j, int nr,
                                                int lane, float mybias, float s0, float inv_norm, hsk_row<V, NCH>& acc,
                                                float& gsum, float& gv, float& xv) {
   static_assert(LOSS == HSK_LOSS_BPR || LOSS == HSK_LOSS_BCE, "the sampled softmax keeps a running max: row by row");
-  if (j >= nr) return;
+  if (!FULL_BUF && j >= nr) return;
   float sv = 0.f;
 #pragma unroll
   for (int r = 0; r < R; ++r)
-    if (j + r < nr) sv = hsk_writelane_f(hsk_wave_sum(hsk_row_dot_partial(ur, buf[r])), j + r, sv);
+    if (FULL_BUF || j + r < nr) sv = hsk_writelane_f(hsk_wave_sum(hsk_row_dot_partial(ur, buf[r])), j + r, sv);
   const float s = sv + mybias;
   float x, g;
   if (LOSS == HSK_LOSS_BPR) {
@@ -174,12 +176,12 @@ __device__ __forceinline__ void hsk_weigh_rows(const hsk_row<V, NCH>& ur, const 
     x = s;
     g = hsk_sigmoid_neg_scaled<TINY>(inv_norm, -s);   // sigma(s)/(B*K), label 0
   }
-  const bool mine = lane >= j && lane < min(j + R, nr);
+  const bool mine = lane >= j && lane < (FULL_BUF ? j + R : min(j + R, nr));
   gv = mine ? g : gv;
   xv = mine ? x : xv;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    if (j + r < nr) {
+    if (FULL_BUF || j + r < nr) {
       const float gr = hsk_readlane_f(g, j + r);
       if (LOSS == HSK_LOSS_BPR) gsum += gr;   // row order
       hsk_row_axpy(acc, gr, buf[r]);

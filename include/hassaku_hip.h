@@ -291,6 +291,12 @@ typedef struct hsk_bprmf_state {
      pass.  0 (default): chosen by the batch's hot set, or by the environment's HSK_ITEM_PAIR = 0 / 1; 1: the pair
      form (128-float slices, two list entries per load) wherever it exists; -1: never.  Bit-identical results */
   int32_t item_pair;
+  /* CALLER-OWNED: the gather loop of the large-batch forward kernels.  0 (default): the library's choice, or the
+     environment's HSK_FWD_OVERLAP = 0 / 1; 1: the overlapped loop (every load of a buffer issued unconditionally, so the
+     other buffer's loads stay in flight while one is weighed) wherever it exists; -1: the loop with a test per row.
+     Bit-identical results */
+  int32_t fwd_overlap;
+  int32_t reserved0;   /* zero; keeps the state free of padding holes */
 } hsk_bprmf_state;
 
 int64_t hsk_bprmf_workspace_bytes(int64_t n_users, int64_t n_items, int64_t dim,
