@@ -87,6 +87,9 @@ SIGNATURES = {
     'hsk_sparse_rows_sum_backward': (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                                              c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
                                              c_void_p]),
+    'hsk_ecf_affiliation': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_double, c_void_p, c_void_p]),
+    'hsk_ecf_affiliation_backward': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_void_p,
+                                             c_void_p]),
     'hsk_adamw_dense': (c_int, [c_void_p] * 4 + [c_int64] + [c_double] * 5 + [c_int64, c_void_p]),
     'hsk_opt_dense': (c_int, [c_int] + [c_void_p] * 4 + [c_int64] + [c_double] * 5 + [c_int64, c_void_p]),
     'hsk_sample_negatives_uniform': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,

@@ -4,7 +4,7 @@ neighbourhood models (uknn, iknn), the linear model (ease), the graph model (p3a
 reference's other algorithms are out of scope, except its neural model (dmf), which trains
 like the other SGD models but on a sparse first layer.
 
-The registry has six families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
+The registry has seven families.  `AlgorithmsEnum` holds the SGD-trained models: iterating it lists those six, as it
 always has.  `SparseAlgorithmsEnum` holds the neighbourhood models, `LinearAlgorithmsEnum` the linear one and
 `GraphAlgorithmsEnum` the random-walk one and `FactorAlgorithmsEnum` the one-shot factorisation (all fitted once on
 the train CSR).  Every family is reachable by name through `AlgorithmsEnum` (`AlgorithmsEnum['iknn']`,
@@ -12,10 +12,14 @@ the train CSR).  Every family is reachable by name through `AlgorithmsEnum` (`Al
 that resolves a slot by name -- run_experiment.py, the experiment helpers -- takes any of them.  `ALGORITHM_NAMES` lists the first two families, `ALL_ALGORITHM_NAMES` the first three and
 `REGISTERED_ALGORITHM_NAMES` the first four and `CLI_ALGORITHM_NAMES` the first five (the earlier tuples keep their
 contents).  `NeuralAlgorithmsEnum` holds `dmf`, trained by the Trainer like the first family;
-`EXPERIMENT_ALGORITHM_NAMES` = `CLI_ALGORITHM_NAMES` + ('dmf',) is what run_experiment.py offers.  Callers use only a slot's `.name` and `.value`.
+`EXPERIMENT_ALGORITHM_NAMES` = `CLI_ALGORITHM_NAMES` + ('dmf',).  `TagAlgorithmsEnum` holds `ecf`, trained by the
+Trainer too, on a dataset that carries the item x tag matrix; `RUNNABLE_ALGORITHM_NAMES` =
+`EXPERIMENT_ALGORITHM_NAMES` + ('ecf',) is what run_experiment.py offers.  Callers use only a slot's `.name` and
+`.value`.
 """
 from enum import Enum, EnumMeta
 
+from hassaku_amd.algorithms.ecf_alg import ECF
 from hassaku_amd.algorithms.graph_algs import P3alpha
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN
 from hassaku_amd.algorithms.linear_algs import EASE
@@ -46,13 +50,17 @@ class NeuralAlgorithmsEnum(Enum):
     dmf = DeepMatrixFactorization
 
 
+class TagAlgorithmsEnum(Enum):
+    ecf = ECF
+
+
 _OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum, GraphAlgorithmsEnum, FactorAlgorithmsEnum,
-                   NeuralAlgorithmsEnum)
+                   NeuralAlgorithmsEnum, TagAlgorithmsEnum)
 
 
 class _RegistryMeta(EnumMeta):
-    """Looks a name up among the SGD slots first, then among the sparse-matrix, the linear, the graph, the factor and
-    the neural slots."""
+    """Looks a name up among the SGD slots first, then among the sparse-matrix, the linear, the graph, the factor, the
+    neural and the tag slots."""
 
     def __getitem__(cls, name):
         if name in cls._member_map_:
@@ -86,3 +94,4 @@ ALL_ALGORITHM_NAMES = ALGORITHM_NAMES + tuple(m.name for m in LinearAlgorithmsEn
 REGISTERED_ALGORITHM_NAMES = ALL_ALGORITHM_NAMES + tuple(m.name for m in GraphAlgorithmsEnum)
 CLI_ALGORITHM_NAMES = REGISTERED_ALGORITHM_NAMES + tuple(m.name for m in FactorAlgorithmsEnum)
 EXPERIMENT_ALGORITHM_NAMES = CLI_ALGORITHM_NAMES + tuple(m.name for m in NeuralAlgorithmsEnum)
+RUNNABLE_ALGORITHM_NAMES = EXPERIMENT_ALGORITHM_NAMES + tuple(m.name for m in TagAlgorithmsEnum)

@@ -52,9 +52,17 @@ def validate_dmf_conf(conf: dict):
     check(conf)
 
 
+def validate_ecf_conf(conf: dict):
+    """The ECF keys of a conf: `embedding_dim`, `n_clusters` (1..64), `top_n`, `top_m` (1..n_clusters), `top_p` (ints),
+    `temp_masking`, `temp_tags` (> 0); absent keys take the constructor's defaults; anything else raises ValueError."""
+    from hassaku_amd.algorithms.ecf_alg import validate_ecf_conf as check
+    check(conf)
+
+
 def parse_conf(conf: dict, alg, dataset) -> dict:
     """alg / dataset are members of AlgorithmsEnum / DatasetsEnum (only .name and alg.value are used)."""
     from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm
+    from hassaku_amd.algorithms.ecf_alg import ECF
     from hassaku_amd.algorithms.graph_algs import P3alpha, validate_p3alpha_conf
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
     from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
@@ -74,6 +82,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
         validate_svd_conf(conf)
     elif issubclass(alg.value, DeepMatrixFactorization):
         validate_dmf_conf(conf)   # its own keys; the SGD defaults below apply as for any trained model
+    elif issubclass(alg.value, ECF):
+        validate_ecf_conf(conf)   # likewise
     conf['alg'] = alg.name
     conf['time_run'] = generate_id()
     conf['dataset'] = dataset.name

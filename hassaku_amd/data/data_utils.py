@@ -15,7 +15,7 @@ from scipy import sparse as sp
 from torch.utils.data import DataLoader
 
 from hassaku_amd.data.dataloader import NegativeSampler, TrainDataLoader
-from hassaku_amd.data.dataset import FullEvalDataset, TrainRecDataset
+from hassaku_amd.data.dataset import ECFTrainRecDataset, FullEvalDataset, TrainRecDataset
 
 
 class DatasetsEnum(enum.Enum):
@@ -46,7 +46,9 @@ class _EvalLoader:
 def get_dataloader(conf: dict, split_set: str):
     running = conf['running_settings']
     if split_set == 'train':
-        dataset = TrainRecDataset(data_path=conf['dataset_path'])
+        # ECF's train dataset also carries the item x tag matrix (data/data_utils.py:325-328)
+        train_dataset_class = ECFTrainRecDataset if conf.get('alg') == 'ecf' else TrainRecDataset
+        dataset = train_dataset_class(data_path=conf['dataset_path'])
         sampler = NegativeSampler(train_dataset=dataset, n_neg=conf['neg_train'],
                                   neg_sampling_strategy=conf['train_neg_strategy'])
         loader = TrainDataLoader(sampler, dataset, batch_size=conf['train_batch_size'], shuffle=True,

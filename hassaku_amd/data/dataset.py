@@ -100,6 +100,28 @@ class TrainRecDataset(RecDataset):
         return self._device_cache[key]
 
 
+class ECFTrainRecDataset(TrainRecDataset):
+    """TrainRecDataset plus the item x tag matrix ECF's tag loss reads (data/dataset.py:228-258): needs tag_idxs.csv and
+    item_tag_idxs.csv (`item_idx`, `tag_idx`) in the dataset directory.  `tag_matrix` is the reference's, by its
+    arithmetic: the int16 0/1 incidence times diag(log(n_items / (tag frequency + 1e-6))), float64 CSR; an unused tag
+    gets the large finite weight log(n_items * 1e6).  `tag_incidence` and `tag_weight` are its two factors."""
+
+    def __init__(self, data_path: str, delete_lhs: bool = True):
+        super().__init__(data_path, delete_lhs)
+        from scipy import sparse as sp
+        tag_idxs = pd.read_csv(os.path.join(data_path, 'tag_idxs.csv'))
+        item_tag_idxs = pd.read_csv(os.path.join(data_path, 'item_tag_idxs.csv'))
+        self.n_tags = len(tag_idxs)
+        self.tag_incidence = sp.csr_matrix(
+            (np.ones(len(item_tag_idxs), dtype=np.int16), (item_tag_idxs.item_idx, item_tag_idxs.tag_idx)),
+            shape=(self.n_items, self.n_tags))
+        tag_frequency = np.array(self.tag_incidence.sum(axis=0)).flatten()
+        self.tag_weight = np.log(self.n_items / (tag_frequency + 1e-6))
+        self.tag_matrix = self.tag_incidence @ sp.diags(self.tag_weight)
+        self.name = 'ECFTrainRecDataset'
+        logging.info('Built %s: %d tags, %d item-tag pairs', self.name, self.n_tags, self.tag_incidence.nnz)
+
+
 class FullEvalDataset(RecDataset):
     """All users against all items.  Ground truth = the split's interactions; excluded from ranking =
     train (val split) or train + val (test split) (data/dataset.py:143-201)."""

@@ -10,11 +10,12 @@ import typing
 
 from hassaku_amd.algorithms.algorithms_utils import AlgorithmsEnum
 from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm, SparseMatrixBasedRecommenderAlgorithm
+from hassaku_amd.algorithms.ecf_alg import ECF
 from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
 from hassaku_amd.conf.conf_parser import parse_conf, parse_conf_file, save_yaml
 from hassaku_amd.data.data_utils import (DatasetsEnum, build_user_and_item_pop_matrix, build_user_and_item_tag_matrix,
                                          get_dataloader)
-from hassaku_amd.data.dataset import TrainRecDataset
+from hassaku_amd.data.dataset import ECFTrainRecDataset, TrainRecDataset
 from hassaku_amd.eval.eval import FullEvaluator, FullEvaluatorCalibrationDecorator, evaluate_recommender_algorithm
 from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 from hassaku_amd.train.trainer import Trainer
@@ -91,6 +92,8 @@ def run_train_val(alg: AlgorithmsEnum, dataset: DatasetsEnum, conf: typing.Union
         return metrics_values, conf
     if not issubclass(alg.value, SGDBasedRecommenderAlgorithm):
         raise ValueError(f'Training for {alg.value} has been not implemented')
+    if issubclass(alg.value, ECF) and world > 1:
+        raise ValueError(f'{alg.name} runs in a single process')
     train_loader = get_dataloader(conf, 'train')
     val_loader = get_dataloader(conf, 'val')
     model = alg.value.build_from_conf(conf, train_loader.dataset)
@@ -115,6 +118,9 @@ def run_test(alg: AlgorithmsEnum, dataset: DatasetsEnum, conf: typing.Union[str,
     if issubclass(alg.value, DeepMatrixFactorization):
         # its towers read the train matrix, which the test split does not hold (experiment_helper.py:103-106)
         model = alg.value.build_from_conf(conf, TrainRecDataset(conf['dataset_path']))
+    elif issubclass(alg.value, ECF):
+        # the train matrix and the tag matrix (experiment_helper.py:107-108)
+        model = alg.value.build_from_conf(conf, ECFTrainRecDataset(conf['dataset_path']))
     else:
         model = alg.value.build_from_conf(conf, test_loader.dataset)
     if isinstance(model, SparseMatrixBasedRecommenderAlgorithm):

@@ -342,6 +342,54 @@ def sparse_rows_sum(Wt: torch.Tensor, csr, idx: torch.Tensor, status=None) -> to
     return _SparseRowsSum.apply(Wt, indptr, indices, idx.contiguous(), status)
 
 
+ECF_MAX_CLUSTERS = 64   # one wavefront lane per taste cluster (HSK_ECF_MAX_CLUSTERS of csrc/hsk_ecf.hip)
+
+
+class _EcfAffiliation(torch.autograd.Function):
+    """A = sigmoid(S) * (p + (m - p)) along the rows of S [n, C], p = softmax(S / temp), m the exact top-k mask with the
+    lower index winning a tie (hsk_ecf_affiliation).  backward = hsk_ecf_affiliation_backward: the gradient passes
+    through p only; nothing but S is saved.  Both directions are deterministic."""
+
+    @staticmethod
+    def forward(ctx, S, top_k, temp):
+        _lib.require_gpu()
+        lib = _lib.load()
+        _chk(S, torch.float32, 'S')
+        if S.dim() != 2:
+            raise ValueError(f'S has shape {tuple(S.shape)}, expected [n, n_clusters]')
+        n, C = S.shape
+        if not 1 <= C <= ECF_MAX_CLUSTERS:
+            raise ValueError(f'S has {C} clusters per row, 1..{ECF_MAX_CLUSTERS} are served')
+        if isinstance(top_k, bool) or int(top_k) != top_k or not 1 <= top_k <= C:
+            raise ValueError(f'top_k must be an integer in [1, {C}], got {top_k!r}')
+        temp = float(temp)
+        if not (temp > 0 and temp != float('inf')):
+            raise ValueError(f'the temperature must be positive and finite, got {temp!r}')
+        A = torch.empty_like(S)
+        _lib.check(lib.hsk_ecf_affiliation(_p(S), n, C, int(top_k), temp, _p(A), _stream()), 'hsk_ecf_affiliation')
+        ctx.save_for_backward(S)
+        ctx.args = (n, C, int(top_k), temp)
+        return A
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        S, = ctx.saved_tensors
+        n, C, top_k, temp = ctx.args
+        G = grad_out.contiguous()
+        _chk(G, torch.float32, 'grad of the affiliations', (n, C))
+        dS = torch.empty_like(S)
+        _lib.check(lib.hsk_ecf_affiliation_backward(_p(S), _p(G), n, C, top_k, temp, _p(dS), _stream()),
+                   'hsk_ecf_affiliation_backward')
+        return dS, None, None
+
+
+def ecf_affiliation(S: torch.Tensor, top_k: int, temp: float) -> torch.Tensor:
+    """Sparse affiliations [n, C] of the rows of similarities S [n, C] (fp32, contiguous, C <= ECF_MAX_CLUSTERS) to
+    their top_k taste clusters; differentiable wrt S with the softmax at temperature `temp` standing in for the mask."""
+    return _EcfAffiliation.apply(S, top_k, temp)
+
+
 def adamw_dense(p, g, m, v, lr, wd, step, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=ADAM_EPS):
     """In-place dense AdamW step (step is 1-based)."""
     _lib.require_gpu()

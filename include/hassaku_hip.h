@@ -149,6 +149,21 @@ int hsk_sparse_rows_sum_backward(const float* g, const int64_t* indptr, const in
                                  hsk_stream_t stream);
 
 /*
+ * The affiliation of ECF (algorithms/sgd_alg.py:676-725): rows of similarities S fp32 [n, C] row-major to sparse
+ * affiliations over C <= 64 taste clusters.  With p = softmax(S / t) along the row and m the exact top-k mask
+ * (m_c = 1 iff fewer than k entries j have S_j > S_c or (S_j == S_c and j < c): the lower index wins a tie),
+ *   hsk_ecf_affiliation           A = sigmoid(S) * (p + (m - p)), the sum in fp32 in this order: exactly 0 off the mask.
+ *   hsk_ecf_affiliation_backward  dS_c = G_c sigmoid'(S_c) (p + (m - p))_c + (1/t) p_c (h_c - sum_j p_j h_j),
+ *                                 h = G * sigmoid(S): the mask passes no gradient (straight-through); p, m and the
+ *                                 sigmoid are recomputed from S.
+ * One wavefront lane per cluster, no atomics: two calls give the same bits.  n == 0 is a no-op.  C outside [1, 64],
+ * k outside [1, C], t <= 0 or a non-finite t: HSK_ERR_INVALID.
+ */
+int hsk_ecf_affiliation(const float* S, int64_t n, int64_t C, int64_t k, double t, float* A, hsk_stream_t stream);
+int hsk_ecf_affiliation_backward(const float* S, const float* G, int64_t n, int64_t C, int64_t k, double t, float* dS,
+                                 hsk_stream_t stream);
+
+/*
  * One dense AdamW step on a flat parameter of n elements -- torch.optim.AdamW defaults
  * (train/trainer.py:52-53,147): p*=1-lr*wd; m=lerp(m,g,1-b1); v=b2*v+(1-b2)g^2;
  * p -= (lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps).  `step` is t (1-based, after increment).
