@@ -483,18 +483,25 @@ class BprMfFusedState:
 
     Parameters are borrowed from the model (`nn.Parameter.data`): the fused step writes into the model's own
     tensors.  With the lazy AdamW (lazy_users, the default; lazy_items on large catalogues) a row outside the batch
-    keeps up to 63 pending zero-gradient steps until it is next touched: call flush() before reading the tables
+    keeps its pending zero-gradient steps until it is next touched or swept -- any number of them: the periodic sweep
+    comes every 64 steps at most for small batches and not at all at the headline shape (flush_cadence()), where rows
+    go hundreds of steps behind: call flush() before reading the tables
     (state_dict(), save_model_to_path(), evaluation) -- Trainer does.  One instance per (model, hyper-parameters).
+
+    start_step: the optimiser's step counter before the first step (resuming a run): rows and moments are taken as
+    current at that step -- preload `m[k]` / `v[k]` (the tensors the C state points at) before the first step.
     """
 
     def __init__(self, user_emb, item_emb, item_bias=None, user_bias=None, global_bias=None, *, lr, wd,
                  max_batch, max_cols, beta1=ADAM_BETA1, beta2=ADAM_BETA2, eps=None, seed=0,
                  csr_indptr=None, csr_indices=None, coo_user=None, coo_item=None, lazy_users='auto', overlap=True,
                  loss='bpr', log_adjust=0.0, alias=None, optimizer='adamw', lazy_items='auto', graph_chunk=0,
-                 flush_every=0):
+                 flush_every=0, start_step=0):
         _lib.require_gpu()
         if optimizer not in OPT_KINDS:
             raise ValueError(f'Optimizer {optimizer} not yet implemented')
+        if int(start_step) < 0:
+            raise ValueError('start_step must be >= 0')
         eps = opt_eps(optimizer, eps)
         self.lib = _lib.load()
         n_users, dim = user_emb.shape
@@ -539,7 +546,7 @@ class BprMfFusedState:
             lazy_items = (dim % 2 == 0 and n_items >= 2 * self.max_batch * self.max_cols
                           and n_items * dim > LAZY_USERS_MIN_ELEMENTS)
         st.lazy_items = 1 if lazy_items else 0
-        st.step = 0
+        st.step = int(start_step)   # hsk_bprmf_init_workspace stamps every row as current at this step
         st.csr_indptr, st.csr_indices = _p(csr_indptr), _p(csr_indices)
         st.coo_user, st.coo_item = _p(coo_user), _p(coo_item)
         st.nnz = 0 if coo_user is None else coo_user.numel()

@@ -113,6 +113,58 @@ def test_opt_dense_on_reference_grads(case):
             assert not m.any()                   # adagrad leaves exp_avg alone
 
 
+DENSE_GRID = 2048 * 256 * 4      # elements one pass of hsk_opt_dense's capped grid covers (float4 per thread)
+
+
+@pytest.fixture(scope='module', params=[1, 2, 3, 4, 5, 7, DENSE_GRID, DENSE_GRID + 1, DENSE_GRID + 3, DENSE_GRID + 4,
+                                        DENSE_GRID + 5])
+def dense_inputs(request):
+    """n, p, non-zero moments and a gradient over 1e-12 .. 1e3 with both signs and exact zeros: built once per size and
+    shared by the three optimisers' cases (pytest runs a module-scoped parameter's cases together)."""
+    n = request.param
+    rng = np.random.RandomState(n % 9973)
+    p = (rng.randn(n) * 0.05).astype(np.float32)
+    m = (rng.randn(n) * 1e-3).astype(np.float32)
+    v = ((0.25 + rng.rand(n)) * 1e-6).astype(np.float32)
+    g = (np.sign(rng.randn(n)) * 10.0 ** rng.uniform(-12, 3, size=n)).astype(np.float32)
+    g[rng.rand(n) < 0.1] = 0.0
+    g[:min(n, 4)] = np.array([1e3, -1e-12, 0.0, -1e3], np.float32)[:min(n, 4)]
+    g[-1] = np.float32(-7.0)                           # a gradient the scalar tail cannot miss
+    return n, p, m, v, g
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('opt', ['adamw', 'adam', 'adagrad'])
+def test_opt_dense_every_tail_and_late_steps(oracle, opt, dense_inputs):
+    """hsk_opt_dense, the optimiser of every autograd-path model, against oracle.opt_step: sizes around the float4 body /
+    scalar tail and one pass of the capped grid (above it the grid-stride loop runs a second round), steps up to far
+    beyond the bias corrections' saturation, preloaded moments, wd = 0 and 1e-2; g = None is a zero gradient, bit for bit."""
+    from hassaku_amd import hip_ops as ops
+    n, p0, m0, v0, g = dense_inputs
+    gd = _dev(g)
+    for step in (1, 2, 1000, 65536, 10 ** 6):
+        for wd in (0.0, 1e-2):
+            p, m, v = _dev(p0.copy()), _dev(m0.copy()), _dev(v0.copy())
+            ops.opt_dense(opt, p, gd, m, v, 1e-3, wd, step)
+            rp, rm, rv = p0.copy(), m0.copy(), v0.copy()
+            oracle.opt_step(opt, rp, g, rm, rv, 1e-3, wd, step)
+            what = (opt, n, step, wd)
+            assert max_norm_err(v.cpu().numpy(), rv) < 1e-6, what
+            if opt == 'adagrad':
+                assert np.array_equal(m.cpu().numpy(), m0), what
+            else:
+                assert max_norm_err(m.cpu().numpy(), rm) < 1e-6, what
+            assert_adam_param_close(p.cpu().numpy(), rp, what, _max_tol(opt))
+            assert not np.array_equal(p.cpu().numpy()[-1:], p0[-1:]), what      # the last element was updated
+    for wd in (0.0, 1e-2):
+        a = [_dev(x.copy()) for x in (p0, m0, v0)]
+        b = [_dev(x.copy()) for x in (p0, m0, v0)]
+        ops.opt_dense(opt, a[0], None, a[1], a[2], 1e-3, wd, 1000)
+        ops.opt_dense(opt, b[0], torch.zeros_like(gd), b[1], b[2], 1e-3, wd, 1000)
+        for x, y in zip(a, b):
+            assert torch.equal(x, y), (opt, n, wd)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('case', G8_CASES)
 def test_fused_step_three_steps_vs_golden(case):
