@@ -716,7 +716,12 @@ int hsk_topk_merge(const float* vals, const int32_t* idx, int64_t n_parts, int64
  * Per-user precision@k, recall@k, ndcg@k for each k in ks (host array, descending or any order)
  * from a ranked list topk_idx [n_rows, k_max] and the ground-truth CSR (sorted rows) of the split:
  * out[r, 3*t+0..2] = precision, recall, ndcg at ks[t].  Semantics of eval/metrics.py:4-105
- * (recall and ndcg are 0 for users without ground truth; ndcg clamped to <= 1).
+ * (recall and ndcg are 0 for users without ground truth; ndcg clamped to <= 1).  Hits are counted per position: an
+ * id that stands twice in a list counts twice (torch.gather), so recall may exceed 1; ids in no label row (the
+ * 0x7fffffff pads of hsk_topk_merge among them) never hit.
+ * There is no status word: a u_idx[r] outside [0, n_users) is NOT reported -- the row is silently scored against the
+ * labels of user 0 (every other evaluation kernel raises HSK_STATUS_BAD_INDEX).  Callers must pass valid ids; both
+ * device loops of eval/eval.py pass contiguous arange ids only.
  */
 #define HSK_MAX_KS 8 /* cut-offs per call of hsk_rank_metrics / hsk_calibration_metrics */
 int hsk_rank_metrics(const int32_t* topk_idx, int64_t n_rows, int64_t k_max,
@@ -778,7 +783,9 @@ int hsk_knn_score_rows(const int64_t* users, int64_t n_users, int64_t n_a_rows, 
 
 /* fp64 top-k of each row of a dense [rows, n_cols] matrix (leading dimension ld), k <= HSK_KNN_MAX_K, order
  * (value desc, index asc); ids int32 (the input of hsk_rank_metrics).  Replaces torch.topk on the masked
- * float64 predictions (eval/eval.py:63). */
+ * float64 predictions (eval/eval.py:63).  Values are ranked by their bit patterns, as in the fp32 selection: -0.0
+ * ranks below +0.0, a NaN with the sign bit clear above +inf and a NaN with the sign bit set below -inf; columns
+ * [n_cols, ld) are never read. */
 int hsk_knn_topk_rows(const double* scores, int64_t rows, int64_t n_cols, int64_t ld, int64_t k, double* out_vals,
                       int32_t* out_idx, hsk_stream_t stream);
 
