@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include "../../include/hassaku_hip.h"
 
@@ -44,6 +45,13 @@ struct hsk_ks {
   int k[HSK_MAX_KS];
   int n;
 };
+
+// an integer switch from the environment (experiments, tests).  The call sites keep the value in a `static`, so a
+// variable is read once per process: changing it afterwards has no effect
+static inline int hsk_env_int(const char* name, int dflt) {
+  const char* s = getenv(name);
+  return s ? atoi(s) : dflt;
+}
 
 static inline int64_t hsk_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t hsk_align_up(int64_t a, int64_t b) { return hsk_ceil_div(a, b) * b; }

@@ -5,7 +5,6 @@
 // (topk(100), k in {100,50,10,5}), eval/metrics.py:4-105 (precision / recall / ndcg).
 #include "hsk_common.h"
 #include "hsk_gemm_wide_h2.h"
-#include <stdlib.h>
 
 #include <algorithm>
 
@@ -179,7 +178,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 static int g_eval_x3 = -1;
 int hsk_eval_x3() {   // also called from hsk_eval_fused.hip
   if (g_eval_x3 < 0) {
-    const int v = getenv("HSK_EVAL_X3") ? atoi(getenv("HSK_EVAL_X3")) : 2;
+    const int v = hsk_env_int("HSK_EVAL_X3", 2);
     g_eval_x3 = v < 0 ? 0 : (v > 2 ? 2 : v);
   }
   return g_eval_x3;
@@ -1299,7 +1298,7 @@ extern "C" int hsk_mf_eval_topk_planes(const float* user_emb, const float* item_
 #define HSK_SCORE_GEMM(KERNEL)                                                                                        \
   KERNEL<<<grid, 256, 0, stream>>>(user_emb, item_emb, item_bias, user_bias, global_bias, (int)n_users, (int)dim, u_idx, \
                                    (int)n_rows, (long long)item_begin, (int)item_count, scores_ws, status)
-  static const int planes_on = getenv("HSK_EVAL_PLANES") ? atoi(getenv("HSK_EVAL_PLANES")) : 1;
+  static const int planes_on = hsk_env_int("HSK_EVAL_PLANES", 1);
   if (x3 && vec4 && planes_on && planes_ws && ((uintptr_t)planes_ws & 255) == 0 &&
       planes_bytes >= hsk_mf_eval_planes_bytes(n_rows, item_count, dim)) {
     // the operands' pieces, made once for the call
@@ -1327,7 +1326,7 @@ extern "C" int hsk_mf_eval_topk_planes(const float* user_emb, const float* item_
     __bf16* Bpl = (__bf16*)((char*)planes_ws + hsk_align_up(6 * (int64_t)a_rows * Dp, 256));
     // 256 x 256 block tiles (one wave per SIMD) once there are enough of them to fill the chip a few times over;
     // below that the 128 x 128 kernel, whose four times as many workgroups fill it sooner.  Same bits either way.
-    static const int wide_on = getenv("HSK_EVAL_WIDE") ? atoi(getenv("HSK_EVAL_WIDE")) : 1;
+    static const int wide_on = hsk_env_int("HSK_EVAL_WIDE", 1);
     const int64_t wide_blocks = hsk_ceil_div(n_rows, GEMM_W_BM) * hsk_ceil_div(item_count, GEMM_W_BN);
     const bool wide = wide_on == 2 || (wide_on && wide_blocks >= 3 * 256);
     hsk_eval_split_planes_k(user_emb, u_idx, 0, n_users, (int)n_rows, a_rows, (int)dim, Apl, stream, wide ? 16 : GEMM_BK);

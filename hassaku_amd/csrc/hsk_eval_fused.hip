@@ -17,7 +17,6 @@
 // top k of a user with fewer than k admissible items, lowest item id first).
 #include "hsk_common.h"
 #include "hsk_gemm_wide_h2.h"
-#include <stdlib.h>
 
 #include <algorithm>
 
@@ -1006,7 +1005,7 @@ static int hsk_fused_splits(int64_t n_rows, int64_t item_count, int64_t k) {
   const int64_t row_blocks = hsk_ceil_div(n_rows, FG_BM), n_tiles = hsk_ceil_div(item_count, FG_BN);
   // two workgroups of this kernel fit a CU (256 VGPRs): 512 of them are one full round; 1024 (two rounds, twice as many
   // lists to warm up) measured 748 vs 804 k users/s at the lfm2b shape, 256: 573 k
-  static const int target_wgs = getenv("HSK_FUSED_WGS") ? atoi(getenv("HSK_FUSED_WGS")) : 512;
+  static const int target_wgs = hsk_env_int("HSK_FUSED_WGS", 512);
   int64_t s = hsk_ceil_div(target_wgs, row_blocks);
   s = std::min<int64_t>(s, 4096 / std::max<int64_t>(k, 1));   // the merge sorts <= 4096 keys per row
   s = std::min<int64_t>(s, std::max<int64_t>(1, n_tiles / 8));   // a split of fewer than 8 tiles is all warm-up
@@ -1020,11 +1019,11 @@ static int hsk_fused_splits(int64_t n_rows, int64_t item_count, int64_t k) {
 // rows hold k candidates).  HSK_FUSED_WIDE: 0 never, 2 whenever the shape allows, 1 (default) by this rule.
 // force: form 2 of the arithmetic -- the fp16-pair core only exists at 256 x 256, so every shape takes this kernel
 static int hsk_fused_wide_splits(int64_t n_rows, int64_t item_count, int64_t k, bool force = false) {
-  static const int wide_env = getenv("HSK_FUSED_WIDE") ? atoi(getenv("HSK_FUSED_WIDE")) : 1;
+  static const int wide_env = hsk_env_int("HSK_FUSED_WIDE", 1);
   const int wide_on = force ? 2 : wide_env;
   if (!wide_on) return 0;
   const int64_t row_blocks = hsk_ceil_div(n_rows, GEMM_W_BM), n_tiles = hsk_ceil_div(item_count, GEMM_W_BN);
-  static const int target_wgs = getenv("HSK_FUSED_WIDE_WGS") ? atoi(getenv("HSK_FUSED_WIDE_WGS")) : 256;
+  static const int target_wgs = hsk_env_int("HSK_FUSED_WIDE_WGS", 256);
   int64_t s = std::max<int64_t>(1, target_wgs / row_blocks);
   s = std::min<int64_t>(s, 4096 / HSK_SEL_KMAX);   // the merge sorts <= 4096 keys per row, HSK_SEL_KMAX per split
   const int64_t min_tiles = wide_on == 2 ? 2 : 16;
@@ -1037,7 +1036,7 @@ static int hsk_fused_wide_splits(int64_t n_rows, int64_t item_count, int64_t k, 
 // columns of the threshold-seeding sample (hsk_eval_seed_thresholds): 0 = no seeding
 static int64_t hsk_fused_seed_cols(int64_t item_count, int64_t k) {
   // (lfm2b shape, one box: no seeding 1.09, 2048 columns 1.11, 4096 columns 1.155 M users/s)
-  static const int seed_on = getenv("HSK_FUSED_SEED") ? atoi(getenv("HSK_FUSED_SEED")) : 4096;
+  static const int seed_on = hsk_env_int("HSK_FUSED_SEED", 4096);
   if (seed_on <= 0 || item_count < 4 * (int64_t)seed_on || k > seed_on / 4) return 0;
   return hsk_align_up(seed_on, GEMM_W_BN);
 }
@@ -1092,7 +1091,7 @@ extern "C" int hsk_mf_eval_topk_fused(const float* user_emb, const float* item_e
   hipStream_t stream = (hipStream_t)stream_;
   {
     // the 256 x 256 / one-wave-per-SIMD kernel: needs the operands' pieces (k-tiles of 16) and enough tiles per split
-    static const int planes_on_w = getenv("HSK_EVAL_PLANES") ? atoi(getenv("HSK_EVAL_PLANES")) : 1;
+    static const int planes_on_w = hsk_env_int("HSK_EVAL_PLANES", 1);
     const bool h2 = hsk_eval_x3() == 2;
     const int SW = hsk_fused_wide_splits(n_rows, item_count, k, h2);
     const bool vec4w = (dim % 4 == 0) && ((((uintptr_t)user_emb | (uintptr_t)item_emb) & 15) == 0);
@@ -1157,7 +1156,7 @@ extern "C" int hsk_mf_eval_topk_fused(const float* user_emb, const float* item_e
       tiles_per_split, excl_indptr, excl_indices, (int)k, SW, slab, SW == 1 ? out_vals : part_vals,                    \
       SW == 1 ? out_idx : part_idx, status, Apl, Bpl, a_rows, b_rows, gthr, dbg, pw, inv_a, inv_b)
 #define HSK_TOPK_WIDE(IB, EX) do { if (h2) HSK_TOPK_WIDE_K(IB, EX, true); else HSK_TOPK_WIDE_K(IB, EX, false); } while (0)
-      static const int dbg = getenv("HSK_FUSED_DEBUG") ? atoi(getenv("HSK_FUSED_DEBUG")) : 0;   // timing experiments
+      static const int dbg = hsk_env_int("HSK_FUSED_DEBUG", 0);   // timing experiments
       const bool extra = user_bias || global_bias;
       if (item_bias) { if (extra) HSK_TOPK_WIDE(true, true); else HSK_TOPK_WIDE(true, false); }
       else           { if (extra) HSK_TOPK_WIDE(false, true); else HSK_TOPK_WIDE(false, false); }
@@ -1188,7 +1187,7 @@ extern "C" int hsk_mf_eval_topk_fused(const float* user_emb, const float* item_e
   int32_t* pi = S == 1 ? out_idx : part_idx;
   // A workspace of hsk_mf_eval_fused_ws_bytes_dim bytes also holds the operands' bf16 pieces: split once, here, instead of
   // once per tile in every workgroup's k loop.  HSK_EVAL_PLANES: 0 off, 2 both operands, 3 items only, 1 (default) by rule.
-  static const int planes_on = getenv("HSK_EVAL_PLANES") ? atoi(getenv("HSK_EVAL_PLANES")) : 1;
+  static const int planes_on = hsk_env_int("HSK_EVAL_PLANES", 1);
   const int64_t plane_bytes = hsk_fused_plane_bytes(n_rows, item_count, dim);
   const bool planes = hsk_eval_x3() && planes_on && vec4 && ws_bytes >= need + plane_bytes;
 #define HSK_SCORE_TOPK(V4, MODE, ...)                                                                                   \

@@ -9,14 +9,12 @@
 //   finish   loss reduction, global bias
 //
 // Reference semantics: one iteration of the loop at train/trainer.py:128-148 of the reference.
-#include <hip/hip_ext.h>
 #include "hsk_sampler.h"
 #include "hsk_sort.h"
 #include "hsk_step_kernels.h"
 #include "hsk_item_sliced.h"
 #include "hsk_fwd_small.h"
 #include "hsk_fwd_part.h"
-#include <stdlib.h>
 
 #include <algorithm>
 #include <utility>
@@ -49,14 +47,14 @@
 // only prepare the next batch.  The per-batch buffers of a set then hold G batches; eager steps use slot 0.
 #define HSK_GROUP_MAX 8
 static int hsk_group_rule(int64_t n_items, int64_t dim, int64_t batch, int64_t n_cols) {
-  static const int env = getenv("HSK_GROUP") ? atoi(getenv("HSK_GROUP")) : HSK_GROUP_MAX;
+  static const int env = hsk_env_int("HSK_GROUP", HSK_GROUP_MAX);
   if (env <= 1 || dim % 2 != 0 || batch > 1024 || !hsk_sort_lds_fits(n_items, batch * n_cols)) return 1;
   return std::min(env, HSK_GROUP_MAX);
 }
 
 static inline int64_t hsk_part_cols(int64_t n_cols, int n_part) { return n_cols + (n_part > 1 ? n_part - 1 : 0); }
 static int hsk_part_rule(int64_t n_items, int64_t dim, int64_t batch, int64_t n_neg, bool lazy_items) {
-  static const int env = getenv("HSK_FWD_PARTS") ? atoi(getenv("HSK_FWD_PARTS")) : 0;
+  static const int env = hsk_env_int("HSK_FWD_PARTS", 0);
   if (env == 1 || lazy_items) return 1;
   // (the partitioned kernel exists for rows of 64 lanes x 4 floats x {1, 2, 4, 8} whole chunks: 256, 512, 1024, 2048 --
   // 768 passed the old `dim % 256 == 0` test and then found no kernel: tools/stress_pipeline.py)
@@ -537,8 +535,7 @@ extern "C" void* hsk_aux_create(void) {
   // latency-bound, letting them through costs the item pass less than a late join costs the step.
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  const char* pe = getenv("HSK_SIDE_PRIO");
-  const int prio = pe ? atoi(pe) : prio_hi;
+  const int prio = hsk_env_int("HSK_SIDE_PRIO", prio_hi);
   bool ok = hipStreamCreateWithPriority(&a->side, hipStreamNonBlocking, prio) == hipSuccess;
   ok = ok && hipStreamCreateWithFlags(&a->cap, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipEventCreate(&a->ev_fork) == hipSuccess;   // a kernel stop event: must be able to take a timestamp
@@ -628,7 +625,7 @@ static int hsk_flush_cadence_rule(double rows, double touched, double dim) {
 // table 0: users, 1: items; touched: rows of that table a step touches
 static int hsk_flush_cadence(const hsk_bprmf_state* st, int table, double touched) {
   if (table == 0 ? !st->lazy_users : !st->lazy_items) return HSK_FLUSH_NEVER;
-  static const int env = getenv("HSK_FLUSH_EVERY") ? atoi(getenv("HSK_FLUSH_EVERY")) : 0;   // experiments
+  static const int env = hsk_env_int("HSK_FLUSH_EVERY", 0);   // experiments
   if (st->flush_every > 0) return st->flush_every;
   if (env > 0) return env;
   const int rule = hsk_flush_cadence_rule((double)(table == 0 ? st->n_users : st->n_items), touched, (double)st->dim);
@@ -650,68 +647,48 @@ extern "C" int32_t hsk_bprmf_flush_cadence(const hsk_bprmf_state* st, int32_t ta
 // =============================================================================================
 // launch sequence
 // =============================================================================================
+// the sweep of one table (parameters, moments, the bias triple, the rows' step counters).  wave: one wave per row
+// (k_row_flush_wave); otherwise a workgroup per row with `vv` floats per thread
+static int hsk_launch_sweep(const hsk_bprmf_state* st, const hsk_ws& w, hipStream_t stream, const hsk_adamw_consts& c,
+                            float* P, float* M, float* V_, float* Pb, float* Mb, float* Vb, int* last, int n_rows,
+                            bool wave, int vv, const int* g_poison) {
+  const int D = (int)st->dim;
+  const bool gen = st->opt_kind != HSK_OPT_ADAMW;
+  if (!wave)
+    return hsk_dispatch_flags([&](auto two_, auto gen_) {
+      k_user_flush<decltype(two_)::value ? 2 : 1, decltype(gen_)::value><<<(unsigned)n_rows, 256, 0, stream>>>(
+          P, M, V_, Pb, Mb, Vb, last, n_rows, D, (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, g_poison);
+      return HSK_OK;
+    }, vv == 2, gen);
+  return hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
+    constexpr int V = decltype(v_)::value, NCH = decltype(n_)::value;
+    constexpr bool FULL = decltype(f_)::value;
+    return hsk_dispatch_flags([&](auto gen_) {
+      k_row_flush_wave<V, NCH, FULL, decltype(gen_)::value><<<(unsigned)((n_rows + 3) / 4), 256, 0, stream>>>(
+          P, M, V_, Pb, Mb, Vb, last, n_rows, D, (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, g_poison);
+      return HSK_OK;
+    }, gen);
+  });
+}
+
 // which: bit 0 = user table, bit 1 = item table (only the lazily updated ones are swept)
 // g_poison: sharded step only (hsk_guard_skip) -- a run that skipped a step for a capacity overflow sweeps nothing
 static int hsk_launch_flush(hsk_bprmf_state* st, const hsk_ws& w, hipStream_t stream, int which = 3,
                             const int* g_poison = nullptr) {
-  const int U = (int)st->n_users, D = (int)st->dim;
+  const int D = (int)st->dim;
   if (st->step == 0) return HSK_OK;
   const hsk_adamw_consts c = hsk_make_adamw_consts(st->lr, st->beta1, st->beta2, st->eps, st->wd, st->step, st->opt_kind);
-#define HSK_FLUSH(VV, GEN)                                                                                       \
-  k_user_flush<VV, GEN><<<(unsigned)U, 256, 0, stream>>>(st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, \
-                                                         st->m_user_bias, st->v_user_bias, w.last_step, U, D,         \
-                                                         (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, g_poison)
-  const bool gen = st->opt_kind != HSK_OPT_ADAMW;
   // one wave per row (k_row_flush_wave) wherever a row fits a wave's registers; HSK_FLUSH_WAVE=0: workgroup per row
-  static const int wave_on = getenv("HSK_FLUSH_WAVE") ? atoi(getenv("HSK_FLUSH_WAVE")) : 1;
+  static const int wave_on = hsk_env_int("HSK_FLUSH_WAVE", 1);
   const bool wave = wave_on && D <= 64 * 8 * ((D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1);
-  auto wave_sweep = [&](float* P, float* M, float* V_, float* Pb, float* Mb, float* Vb, int* last, int n_rows) {
-    return hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
-      constexpr int V = decltype(v_)::value, NCH = decltype(n_)::value;
-      constexpr bool FULL = decltype(f_)::value;
-      const unsigned grid = (unsigned)((n_rows + 3) / 4);
-      if (gen)
-        k_row_flush_wave<V, NCH, FULL, true><<<grid, 256, 0, stream>>>(P, M, V_, Pb, Mb, Vb, last, n_rows, D, (int)st->step, c,
-                                                                     w.adam_tab, HSK_ADAM_TAB_LEN, g_poison);
-      else
-        k_row_flush_wave<V, NCH, FULL, false><<<grid, 256, 0, stream>>>(P, M, V_, Pb, Mb, Vb, last, n_rows, D, (int)st->step, c,
-                                                                      w.adam_tab, HSK_ADAM_TAB_LEN, g_poison);
-      return HSK_OK;
-    });
-  };
-  if (wave) {
-    if (st->lazy_users && (which & 1)) {
-      const int rc = wave_sweep(st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, st->m_user_bias, st->v_user_bias,
-                                w.last_step, U);
-      if (rc != HSK_OK) return rc;
-    }
-    if (st->lazy_items && (which & 2)) {
-      const int rc = wave_sweep(st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias, st->m_item_bias, st->v_item_bias,
-                                w.last_step_i, (int)st->n_items);
-      if (rc != HSK_OK) return rc;
-    }
-    HSK_LAUNCH_CHECK();
-    return HSK_OK;
-  }
-  if (st->lazy_users && (which & 1)) {
-    if (D % 2 == 0) {
-      if (gen) HSK_FLUSH(2, true); else HSK_FLUSH(2, false);
-    } else {
-      if (gen) HSK_FLUSH(1, true); else HSK_FLUSH(1, false);
-    }
-  }
-#undef HSK_FLUSH
-  if (st->lazy_items && (which & 2)) {   // the same sweep over the item table (even dim guaranteed by hsk_check_state)
-    const int I = (int)st->n_items;
-    if (gen)
-      k_user_flush<2, true><<<(unsigned)I, 256, 0, stream>>>(st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias,
-                                                            st->m_item_bias, st->v_item_bias, w.last_step_i, I, D,
-                                                            (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, g_poison);
-    else
-      k_user_flush<2, false><<<(unsigned)I, 256, 0, stream>>>(st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias,
-                                                             st->m_item_bias, st->v_item_bias, w.last_step_i, I, D,
-                                                             (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, g_poison);
-  }
+  int rc = HSK_OK;
+  if (st->lazy_users && (which & 1))
+    rc = hsk_launch_sweep(st, w, stream, c, st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, st->m_user_bias,
+                          st->v_user_bias, w.last_step, (int)st->n_users, wave, D % 2 == 0 ? 2 : 1, g_poison);
+  if (rc == HSK_OK && st->lazy_items && (which & 2))   // the same sweep over the item table (even dim guaranteed by hsk_check_state)
+    rc = hsk_launch_sweep(st, w, stream, c, st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias, st->m_item_bias,
+                          st->v_item_bias, w.last_step_i, (int)st->n_items, wave, 2, g_poison);
+  if (rc != HSK_OK) return rc;
   HSK_LAUNCH_CHECK();
   return HSK_OK;
 }
@@ -732,6 +709,52 @@ static int hsk_periodic_flush(hsk_bprmf_state* st, const hsk_ws& w, hipStream_t 
   int rc = HSK_OK;
   HSK_STAGE(HSK_STAGE_USER, rc = hsk_launch_flush(st, w, stream, which, g_poison));
   return rc;
+}
+
+// the merged launch: item pass + the owners' user-row update (+ the ahead-of-time replay of the next batch's rows), in
+// the form hsk_launch_item_pass chose (whole_rows / part / pair); nblk: the item workgroups
+template <int V, int NCH, bool FULL>
+static void hsk_launch_item_user(const hsk_item_args& ia, const hsk_user_lazy_args& ua, const hsk_ahead_args& ahead,
+                                 const hsk_ride_item* ri, unsigned nblk, bool whole_rows, bool part, bool pair, bool gen,
+                                 bool lazy, hipStream_t stream) {
+  constexpr int VSC = (V == 4) ? 4 : 2;
+  const int dense = ua.n_users > 0;
+  const int nub = (int)hsk_align_up(hsk_ceil_div(dense ? ua.n_users : ua.B, 4) + 1, 8);
+  // ahead workgroups (4 entries each) in octets, one after every `stride` octets of item workgroups; what does not
+  // fit that pattern is dropped (the forward replays those rows itself)
+  const int item_oct = (int)(nblk / 8);
+  int n_ahead_oct = ahead.coo_user ? (int)hsk_ceil_div(hsk_ceil_div(ahead.n, 4), 8) : 0;
+  n_ahead_oct = std::min(n_ahead_oct, item_oct);
+  const int stride = n_ahead_oct ? item_oct / n_ahead_oct : 0;
+  const int nab_big = ahead.coo_user ? (int)hsk_align_up(hsk_ceil_div(ahead.n, 4), 8) : 0;   // large-batch kernel
+
+  if (pair) {
+    if constexpr (V == 4) {
+      if (part) {
+        if constexpr (FULL)
+          k_item_user_pair<NCH, FULL, true><<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, stream>>>(
+              ia, ua, nub, dense, ri ? *ri : hsk_ride_item{});
+      } else {
+        k_item_user_pair<NCH, FULL><<<nblk + (unsigned)nub, 256, 0, stream>>>(ia, ua, nub, dense);
+      }
+    }
+    return;
+  }
+  hsk_dispatch_flags([&](auto gen_, auto lz_) {
+    constexpr bool GEN = decltype(gen_)::value, LZ = decltype(lz_)::value;
+    if (whole_rows)
+      k_item_user_small<V, NCH, FULL, GEN, LZ><<<nblk + (unsigned)(nub + 8 * n_ahead_oct), 256, 0, stream>>>(
+          ia, ua, nub, dense, ahead, n_ahead_oct, stride);
+    else if (part) {
+      if constexpr (V == 4 && FULL && !LZ)
+        k_item_user<V, NCH, FULL, VSC, GEN, LZ, true>
+            <<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, stream>>>(
+                ia, ua, nub, dense, ahead, 0, ri ? *ri : hsk_ride_item{});
+    } else
+      k_item_user<V, NCH, FULL, VSC, GEN, LZ><<<nblk + (unsigned)(nub + (LZ ? nab_big : 0)), 256, 0, stream>>>(
+          ia, ua, nub, dense, ahead, LZ ? nab_big : 0);
+    return HSK_OK;
+  }, gen, lazy);
 }
 
 // Item-major pass (gradient reduction [+ AdamW]).  Even D: the D-sliced, XCD-affine kernel with the widest slice the
@@ -764,11 +787,11 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
   const int vs = VSC;
   int n_sl = (int)hsk_ceil_div(D, 64 * vs);
   // merged launch at a small batch: whole-row item workgroups (n_slices_pad = 0 tells the kernel), see hsk_item_row_body
-  static const int rows_on = getenv("HSK_ITEM_ROWS") ? atoi(getenv("HSK_ITEM_ROWS")) : 1;
+  static const int rows_on = hsk_env_int("HSK_ITEM_ROWS", 1);
   // lazy item AdamW (catalogues far beyond the caches): whole rows as well -- the launch is p / m / v traffic on the
   // touched rows, 2 KB contiguous per row and table instead of two 1 KB halves (hbm workload: 1042 -> 977 us), and the
   // slices' L2 affinity buys nothing for a gather that is a tenth of the bytes
-  static const int rows_lazy = getenv("HSK_ITEM_ROWS_LAZY") ? atoi(getenv("HSK_ITEM_ROWS_LAZY")) : 1;
+  static const int rows_lazy = hsk_env_int("HSK_ITEM_ROWS_LAZY", 1);
   const bool whole_rows = APPLY && ua && rows_on && (n_entries <= 64 * 1024 || (rows_lazy && st->lazy_items)) && !part;
   const bool lazy = APPLY && st->lazy_items;
   const bool gen = APPLY && st->opt_kind != HSK_OPT_ADAMW;   // APPLY == false never calls the update
@@ -777,7 +800,7 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
   // x min(D, 256) floats of user rows per XCD, is more than half an L2, and the lists average a full group of loads
   // (8 entries; the ml10m shape's 39 gain, the lfm2b shape's 3 lose 7 % with the form forced on).  st->item_pair
   // (1 / -1) and HSK_ITEM_PAIR (1 / 0) force it on / off, the state's field first.
-  static const int pair_env = getenv("HSK_ITEM_PAIR") ? atoi(getenv("HSK_ITEM_PAIR")) : -1;
+  static const int pair_env = hsk_env_int("HSK_ITEM_PAIR", -1);
   // (partitions exist for whole chunks only -- hsk_part_rule: D = 256, 512, 1024, 2048, so V == 4 && FULL; a forced
   // st->item_pair on any other partitioned row would find no kernel, so it is not taken there)
   bool pair = false;
@@ -798,73 +821,35 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
                             ua ? ua->desc : nullptr, ua ? ua->rel : 0, w.adam_tab, HSK_ADAM_TAB_LEN, n_part};
   const unsigned nblk = groups * (whole_rows ? 1 : n_slices_pad);
   if (APPLY && ua) {
-    const int dense = ua->n_users > 0;
-    const int nub = (int)hsk_align_up(hsk_ceil_div(dense ? ua->n_users : ua->B, 4) + 1, 8);
-    const hsk_ahead_args ahead = aa ? *aa : hsk_ahead_args{};
-    // ahead workgroups (4 entries each) in octets, one after every `stride` octets of item workgroups; what does not
-    // fit that pattern is dropped (the forward replays those rows itself)
-    const int item_oct = (int)(nblk / 8);
-    int n_ahead_oct = ahead.coo_user ? (int)hsk_ceil_div(hsk_ceil_div(ahead.n, 4), 8) : 0;
-    n_ahead_oct = std::min(n_ahead_oct, item_oct);
-    const int stride = n_ahead_oct ? item_oct / n_ahead_oct : 0;
-    const int nab_big = ahead.coo_user ? (int)hsk_align_up(hsk_ceil_div(ahead.n, 4), 8) : 0;   // large-batch kernel
-
-    if (pair) {
-      if constexpr (APPLY && V == 4) {
-        if (part) {
-          if constexpr (FULL)
-            k_item_user_pair<NCH, FULL, true><<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, stream>>>(
-                ia, *ua, nub, dense, ri ? *ri : hsk_ride_item{});
-        } else {
-          k_item_user_pair<NCH, FULL><<<nblk + (unsigned)nub, 256, 0, stream>>>(ia, *ua, nub, dense);
-        }
-      }
-      return;
-    }
-#define HSK_ITEM_USER(VS, GEN, LZ)                                                                             \
-  do {                                                                                                         \
-    if (whole_rows)                                                                                            \
-      k_item_user_small<V, NCH, FULL, GEN, LZ><<<nblk + (unsigned)(nub + 8 * n_ahead_oct), 256, 0, stream>>>(    \
-          ia, *ua, nub, dense, ahead, n_ahead_oct, stride);                                                    \
-    else if (part) {                                                                                           \
-      if constexpr (V == 4 && FULL && !LZ)                                                                      \
-        k_item_user<V, NCH, FULL, VS, GEN, LZ, true><<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, \
-                                                       stream>>>(ia, *ua, nub, dense, ahead, 0,                \
-                                                                 ri ? *ri : hsk_ride_item{});                  \
-    } else                                                                                                     \
-      k_item_user<V, NCH, FULL, VS, GEN, LZ><<<nblk + (unsigned)(nub + (LZ ? nab_big : 0)), 256, 0, stream>>>(   \
-          ia, *ua, nub, dense, ahead, LZ ? nab_big : 0);                                                       \
-  } while (0)
-    if (gen) { if (lazy) HSK_ITEM_USER(VSC, true, true); else HSK_ITEM_USER(VSC, true, false); }
-    else     { if (lazy) HSK_ITEM_USER(VSC, false, true); else HSK_ITEM_USER(VSC, false, false); }
-#undef HSK_ITEM_USER
+    if constexpr (APPLY)
+      hsk_launch_item_user<V, NCH, FULL>(ia, *ua, aa ? *aa : hsk_ahead_args{}, ri, nblk, whole_rows, part, pair, gen, lazy,
+                                         stream);
     return;
   }
   // lazy item AdamW without the user update in the launch (the sharded step): whole rows, as in the merged launch above
   // (one rank's share of configs[4], 73 % of the 1.25 M x 4 KB rows touched per step: item pass 5.34 -> 4.88 ms, which is
   // what makes the lazy update the faster one there: 7.55-7.63 against 7.92 ms per step for the dense sweep)
-  static const int rows_shard = getenv("HSK_ITEM_ROWS_SHARD") ? atoi(getenv("HSK_ITEM_ROWS_SHARD")) : 1;
+  static const int rows_shard = hsk_env_int("HSK_ITEM_ROWS_SHARD", 1);
   if (APPLY && !part && lazy && rows_shard) {
     const unsigned nb = (unsigned)hsk_ceil_div(n_list, 4);
     hsk_item_args ir = ia;
     ir.n_slices_pad = 0;
-    if constexpr (APPLY) {
-      if (gen) k_item_update_rows<V, NCH, FULL, true, true><<<nb, 256, 0, stream>>>(ir, g_ovf, g_poison);
-      else     k_item_update_rows<V, NCH, FULL, false, true><<<nb, 256, 0, stream>>>(ir, g_ovf, g_poison);
-    }
+    if constexpr (APPLY)
+      hsk_dispatch_flags([&](auto gen_) {
+        k_item_update_rows<V, NCH, FULL, decltype(gen_)::value, true><<<nb, 256, 0, stream>>>(ir, g_ovf, g_poison);
+        return HSK_OK;
+      }, gen);
     return;
   }
-#define HSK_ITEM_SLICED(VS, GEN, LZ)                                                   \
-  do {                                                                                 \
-    if (part) {                                                                        \
-      if constexpr (APPLY && V == 4 && FULL && !LZ)                                    \
-        k_item_update_sliced<APPLY, VS, GEN, LZ, true><<<nblk, 256, 0, stream>>>(ia, g_ovf, g_poison);   \
-    } else                                                                             \
-      k_item_update_sliced<APPLY, VS, GEN, LZ><<<nblk, 256, 0, stream>>>(ia, g_ovf, g_poison);          \
-  } while (0)
-  if (gen) { if (lazy) HSK_ITEM_SLICED(VSC, true, true); else HSK_ITEM_SLICED(VSC, true, false); }
-  else     { if (lazy) HSK_ITEM_SLICED(VSC, false, true); else HSK_ITEM_SLICED(VSC, false, false); }
-#undef HSK_ITEM_SLICED
+  hsk_dispatch_flags([&](auto gen_, auto lz_) {
+    constexpr bool GEN = decltype(gen_)::value, LZ = decltype(lz_)::value;
+    if (part) {
+      if constexpr (APPLY && V == 4 && FULL && !LZ)
+        k_item_update_sliced<APPLY, VSC, GEN, LZ, true><<<nblk, 256, 0, stream>>>(ia, g_ovf, g_poison);
+    } else
+      k_item_update_sliced<APPLY, VSC, GEN, LZ><<<nblk, 256, 0, stream>>>(ia, g_ovf, g_poison);
+    return HSK_OK;
+  }, gen, lazy);
 }
 
 // 1 / (number of terms the loss averages over)
@@ -969,7 +954,7 @@ static int hsk_discard_prefetch(hsk_bprmf_state* st, const hsk_ws& w_all, hipStr
 // the chip mostly idle and the step is launch-latency-bound: fork as early as possible (B=128: 65 us before, 97 us
 // after, 83 us without).
 static bool hsk_pf_early(int64_t B) {
-  static const int env = getenv("HSK_PF_EARLY") ? atoi(getenv("HSK_PF_EARLY")) : -1;   // experiments: 0 / 1 force
+  static const int env = hsk_env_int("HSK_PF_EARLY", -1);   // experiments: 0 / 1 force
   return env >= 0 ? env != 0 : B < 2048;
 }
 #define HSK_PREFETCH_MIN_ENTRIES 4096
@@ -1006,7 +991,7 @@ static int hsk_launch_prefetch(hsk_bprmf_state* st, const hsk_ws& w_all, int set
   }
   if (prc) return prc;
   {   // experiment (HSK_SIDE_DUMMY=n): n empty launches behind the sort -- what a kernel boundary on the side stream costs
-    static const int n_dummy = getenv("HSK_SIDE_DUMMY") ? atoi(getenv("HSK_SIDE_DUMMY")) : 0;
+    static const int n_dummy = hsk_env_int("HSK_SIDE_DUMMY", 0);
     for (int i = 0; i < n_dummy && !aux->g_desc; ++i) k_fill_i32<<<1, 64, 0, aux->side>>>(nullptr, 0, 0);
   }
   HSK_HIP(hipEventRecord(aux->ev_ready, aux->side));
@@ -1020,89 +1005,134 @@ static int hsk_launch_prefetch(hsk_bprmf_state* st, const hsk_ws& w_all, int set
   return HSK_OK;
 }
 
-// stages after prep filled u32 / it32 / owner / cnt of `w` (and, with sorted == true, the item sort too)
-// n_part > 1: batch rows in the partitioned layout (the positive in n_part columns) -> item-partitioned forward
-// slot: the batch's slot inside the set (grouped preparation)
-static int hsk_run_step(hsk_bprmf_state* st, const hsk_ws& w_all, int set, bool sorted, int64_t B, int64_t K,
-                        hipStream_t stream, int n_part = 1, int slot = 0) {
-  const hsk_ws w = hsk_select(w_all, set, slot);
-  const int64_t K_real = K;
-  K = hsk_part_cols(K_real, n_part);   // columns of the batch rows: the positive n_part times (k_prep_sample)
-  const int64_t total = B * K;
-  const int U = (int)st->n_users, D = (int)st->dim;
-  st->step += 1;
-  const hsk_adamw_consts c = hsk_make_adamw_consts(st->lr, st->beta1, st->beta2, st->eps, st->wd, st->step, st->opt_kind);
-  const double inv_bn_d = hsk_loss_norm(st->loss_kind, (double)B, (double)K_real);
-  const float inv_bn = (float)inv_bn_d;
-  hsk_aux* aux = (hsk_aux*)st->aux;
-  const bool gen = st->opt_kind != HSK_OPT_ADAMW;   // generic optimiser arithmetic instead of the AdamW-only kernels
-  if (aux) {
-    aux->cur_set = aux->last_set = set;
-    aux->cur_slot = aux->last_slot = slot;
-  }
-  if (!sorted) {
-    int src = hsk_launch_sort(st, w, total, stream);
-    if (src) return src;
-  }
-  if (st->lazy_items) {
-    // the forward must read current item rows too: replay the missed zero-gradient steps of this batch's items
-    // (the list the sort left in w.touched)
-    const unsigned nblk = (unsigned)std::min<int64_t>(st->n_items, total);
-    if (gen)
-      HSK_STAGE(HSK_STAGE_ITEM, (k_item_catch_up<2, true><<<nblk, 256, 0, stream>>>(
-                                    st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias, st->m_item_bias,
-                                    st->v_item_bias, w.touched, w.n_touched, w.last_step_i, D, (int)st->step, c,
-                                    w.adam_tab, HSK_ADAM_TAB_LEN, aux ? aux->g_desc : nullptr, aux ? aux->g_rel : 0, w.pend)));
-    else
-      HSK_STAGE(HSK_STAGE_ITEM, (k_item_catch_up<2, false><<<nblk, 256, 0, stream>>>(
-                                    st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias, st->m_item_bias,
-                                    st->v_item_bias, w.touched, w.n_touched, w.last_step_i, D, (int)st->step, c,
-                                    w.adam_tab, HSK_ADAM_TAB_LEN, aux ? aux->g_desc : nullptr, aux ? aux->g_rel : 0, w.pend)));
-    HSK_LAUNCH_CHECK();
-  }
-  if (hsk_pf_early(B)) {
-    int prc = hsk_launch_prefetch(st, w_all, set, stream);
-    if (prc) return prc;
-  }
-  // late fork: the fork event is the forward kernel's own completion signal (an ordinary event record in a capture)
-  const bool capturing = aux && aux->g_desc;
-  const hsk_step_desc* gdesc = capturing ? aux->g_desc : nullptr;
-  const int grel = capturing ? aux->g_rel : 0;
-  const bool late_fork = !hsk_pf_early(B) && hsk_prefetch_wanted(st);
-  hipEvent_t fork_ev = (late_fork && !capturing) ? aux->ev_fork : nullptr;
+// stage timing brackets every timing_every-th step: armed before the step that takes the counter to st->step + 1
+static inline void hsk_timing_arm(hsk_bprmf_state* st) {
+  st->timing_now = st->timing && (st->timing_every <= 1 || ((st->step + 1) % st->timing_every) == 0);
+}
 
-  hipEvent_t timed_fwd_end = nullptr;   // a timed step: the forward launch's stop event doubles as the fork event
-  int rc = hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
-    constexpr int V = decltype(v_)::value;
-    constexpr int NCH = decltype(n_)::value;
+// what the launches of one training step share (hsk_run_step fills it, the step's launch functions read it)
+struct hsk_step_ctx {
+  hsk_ws w;                  // the step's buffer set and slot in the primary slots
+  int64_t B, K;              // K: columns of the batch rows, the positive n_part times (k_prep_sample)
+  int D, n_part;
+  hsk_adamw_consts c;
+  double inv_bn_d;           // 1 / (terms the loss averages over)
+  float inv_bn;              // ... as the forward takes it
+  bool gen;                  // generic optimiser arithmetic instead of the AdamW-only kernels
+  bool capturing;            // the sequence is being captured: per-step scalars from gdesc + grel, launches carry no events
+  const hsk_step_desc* gdesc;
+  int grel;
+};
+
+// k_user_catch_up over the rows that `slots[0 .. n)` name, up to `step` - 1: the single-GPU step's stand-alone catch-up
+// (the batch's users) and the sharded step's (the rows requested through a buffer set, which also brings the duplicate
+// lists and the overflow guard words, hsk_guard_skip)
+static void hsk_launch_user_catch_up(const hsk_bprmf_state* st, const hsk_ws& w, hipStream_t stream, const int* slots, int n,
+                                     int64_t step, const hsk_adamw_consts& c, int* dupcnt = nullptr, int* duplist = nullptr,
+                                     const int* g_ovf = nullptr, int* g_poison = nullptr, int g_open = 0) {
+  const int D = (int)st->dim;
+  hsk_dispatch_flags([&](auto two_, auto gen_) {
+    k_user_catch_up<decltype(two_)::value ? 2 : 1, decltype(gen_)::value><<<(unsigned)n, 256, 0, stream>>>(
+        st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, st->m_user_bias, st->v_user_bias, slots, w.owner,
+        w.last_step, n, D, (int)step, c, w.adam_tab, HSK_ADAM_TAB_LEN, dupcnt, duplist, g_ovf, g_poison, g_open);
+    return HSK_OK;
+  }, D % 2 == 0, st->opt_kind != HSK_OPT_ADAMW);
+}
+
+// lazy item AdamW: replay the missed zero-gradient steps of the batch's items (the list the sort left in w.touched), so
+// that the forward reads current rows.  wide: four floats per thread instead of two
+static void hsk_launch_item_catch_up(const hsk_bprmf_state* st, const hsk_ws& w, hipStream_t stream, unsigned nblk, bool wide,
+                                     int64_t step, const hsk_adamw_consts& c, const hsk_step_desc* desc, int rel,
+                                     const int* g_ovf = nullptr, const int* g_poison = nullptr) {
+  hsk_dispatch_flags([&](auto wide_, auto gen_) {
+    k_item_catch_up<decltype(wide_)::value ? 4 : 2, decltype(gen_)::value><<<nblk, 256, 0, stream>>>(
+        st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias, st->m_item_bias, st->v_item_bias, w.touched,
+        w.n_touched, w.last_step_i, (int)st->dim, (int)step, c, w.adam_tab, HSK_ADAM_TAB_LEN, desc, rel, w.pend, g_ovf,
+        g_poison);
+    return HSK_OK;
+  }, wide, st->opt_kind != HSK_OPT_ADAMW);
+}
+
+// Catch-up AHEAD of time (hsk_user_ahead_body): the next batch -- the prefetch's, or the pending hint's -- whose user rows
+// a launch of this step can bring up to date.  false (and *aa untouched): there is none, or HSK_AHEAD=0 turns it off.
+static bool hsk_make_ahead(const hsk_bprmf_state* st, const hsk_step_ctx& cx, const hsk_aux* aux, hsk_ahead_args* aa) {
+  static const int ahead_on = hsk_env_int("HSK_AHEAD", 1);
+  if (!(st->lazy_users && aux && ahead_on && (aux->pf_valid || aux->hint_valid))) return false;
+  const bool pf = aux->pf_valid;
+  *aa = hsk_ahead_args{st->coo_user, pf ? aux->pf_order : aux->hint_order, pf ? aux->pf_start : aux->hint_start,
+                       (int)(pf ? aux->pf_batch : aux->hint_batch), cx.w.stamp, cx.w.claim, st->user_emb, st->m_user_emb,
+                       st->v_user_emb, st->user_bias, st->m_user_bias, st->v_user_bias, cx.w.last_step, cx.D,
+                       (int)st->step, cx.c, cx.w.adam_tab, HSK_ADAM_TAB_LEN, cx.gdesc, cx.grel};
+  return true;
+}
+
+// item-partitioned forward; the NEXT batch's user rows are brought up to date by leading workgroups of the same
+// launch (pure VALU work beside a kernel that waits on the L2 / the fabric), see hsk_fwd_part.h
+// apart: a stand-alone catch-up launch went in front (no ahead-of-time replay then); beg / end: as for hsk_launch_ev
+template <int V, int NCH, bool FULL>
+static int hsk_launch_fwd_part(const hsk_bprmf_state* st, const hsk_step_ctx& cx, hipStream_t stream,
+                               const hsk_lazy_user_args& lz, bool apart, hipEvent_t beg, hipEvent_t end) {
+  if constexpr (V == 4 && FULL) {
+    constexpr int RP = (V * NCH >= 16) ? 2 : HSK_FWD_PART_R;
+    const hsk_aux* aux = (const hsk_aux*)st->aux;
+    const hsk_ws& w = cx.w;
+    const int n_part = cx.n_part;
+    hsk_ahead_args aa = {};
+    int n_ahead = 0;
+    if (!apart && hsk_make_ahead(st, cx, aux, &aa)) n_ahead = (int)hsk_align_up(hsk_ceil_div(aa.n, 4), 8);
+    const unsigned n_unit = 8u * (unsigned)hsk_ceil_div(hsk_ceil_div(cx.B, 4), 8 / n_part);
+    // HSK_AHEAD_MIX=1: the ahead octets interleaved with the unit octets instead of leading (measured: 88 vs 86 us)
+    static const int ahead_mix = hsk_env_int("HSK_AHEAD_MIX", 0);
+    const int stride = (ahead_mix && n_ahead > 0) ? (int)(n_unit / 8) / (n_ahead / 8) : 0;
+    const hsk_part_args pa = {n_part, (int)st->n_items, n_ahead, stride};
+    const hsk_ride_fwd rf = (aux && aux->ride_fwd) ? *aux->ride_fwd : hsk_ride_fwd{};   // riding preparation phases
+    const unsigned grid = (unsigned)rf.n_total + (unsigned)n_ahead + n_unit;
+    // the overlapped gather loop (hsk_fwd_part.h: OVL) or the loop with a test per row: st->fwd_overlap (1 / -1) and
+    // HSK_FWD_OVERLAP (1 / 0) force it on / off, the state's field first; same bits either way
+    static const int ovl_env = hsk_env_int("HSK_FWD_OVERLAP", -1);
+    const bool ovl = st->fwd_overlap ? st->fwd_overlap > 0 : ovl_env >= 0 ? ovl_env != 0 : HSK_FWD_OVERLAP_DEFAULT != 0;
+    // (bpr and bce epilogues only: hsk_part_rule_st keeps sampled softmax away from the partitioned forward)
+    return hsk_dispatch_loss<false>(st->loss_kind, [&](auto lk_) {
+      return hsk_dispatch_flags([&](auto gen_, auto ovl_) {
+        hsk_launch_ev(k_fwd_part<V, NCH, FULL, RP, decltype(lk_)::value, decltype(gen_)::value, decltype(ovl_)::value>,
+                      dim3(grid), dim3(256), 0, stream, cx.capturing, beg, end, st->user_emb, st->item_emb,
+                      st->item_bias, w.u32, w.it32, (int)cx.B, (int)cx.K, cx.D, cx.inv_bn, w.g_s, w.dUb, w.loss_b, lz, pa,
+                      aa, rf);
+        return HSK_OK;
+      }, cx.gen, ovl);
+    });
+  } else {
+    hsk_set_error("internal: item-partitioned forward selected for dim %d", cx.D);
+    return HSK_ERR_UNSUPPORTED;
+  }
+}
+
+// The forward of a step: gather + scores + loss + user-row gradient, one of k_fwd_part, k_fwd_ugrad_wg and k_fwd_ugrad.
+// fork_ev: the event a late prefetch forks on (NULL: none).  *timed_fwd_end: on a timed step, the stop event of the timed
+// launch, which then doubles as the fork event.
+static int hsk_launch_forward(hsk_bprmf_state* st, const hsk_step_ctx& cx, hipStream_t stream, hipEvent_t fork_ev,
+                              hipEvent_t* timed_fwd_end) {
+  const hsk_ws& w = cx.w;
+  const int64_t B = cx.B, K = cx.K;
+  const int D = cx.D;
+  return hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) -> int {
+    constexpr int V = decltype(v_)::value, NCH = decltype(n_)::value, R = (V * NCH >= 16) ? 2 : HSK_FWD_R;
     constexpr bool FULL = decltype(f_)::value;
-    constexpr int R = (V * NCH >= 16) ? 2 : HSK_FWD_R;
     // lazy user AdamW: the forward replays the pending zero-gradient steps of its user row in registers and leaves
     // the current row in ucur (no separate catch-up launch, no rewrite of the row before the owner's update).
     // st->catchup_apart: a stand-alone catch-up launch in front instead -- at B = 4096 the replay is ~9 us of pure VALU
     // work at the head of every forward wave (forward 103 -> 112 us) but the extra launch costs more than it saves
     // (224.5 vs 219.3 us per step), so it is off by default; with it the forward is the pure gather.
-    const bool apart = st->lazy_users && !capturing && st->catchup_apart != 0;
-    if (apart) {
-#define HSK_CATCH_UP(VV, GEN)                                                                                     \
-  HSK_STAGE(HSK_STAGE_USER, (k_user_catch_up<VV, GEN><<<(unsigned)B, 256, 0, stream>>>(                            \
-                                st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, st->m_user_bias,      \
-                                st->v_user_bias, w.u32, w.owner, w.last_step, (int)B, D, (int)st->step, c,         \
-                                w.adam_tab, HSK_ADAM_TAB_LEN, nullptr, nullptr)))
-      if (D % 2 == 0) {
-        if (gen) HSK_CATCH_UP(2, true); else HSK_CATCH_UP(2, false);
-      } else {
-        if (gen) HSK_CATCH_UP(1, true); else HSK_CATCH_UP(1, false);
-      }
-#undef HSK_CATCH_UP
-    }
+    const bool apart = st->lazy_users && !cx.capturing && st->catchup_apart != 0;
+    if (apart) HSK_STAGE(HSK_STAGE_USER, hsk_launch_user_catch_up(st, w, stream, w.u32, (int)B, st->step, cx.c));
     // The forward kernel is launched through hipExtLaunchKernelGGL, whose start / stop events are the dispatch's own
     // timestamps: on a timed step they ARE the stage timing (kernel time as rocprofv3 reports it, no barrier packets
     // around the launch); otherwise the stop event is the prefetch's fork event.
     hsk_lazy_user_args lz = {};
     if (st->lazy_users)
       lz = hsk_lazy_user_args{st->m_user_emb, st->v_user_emb, w.last_step, w.owner, w.dupcnt, w.duplist, w.ucur,
-                              w.mcur, w.vcur, (int)st->step, gen ? 1 : 0, c, w.adam_tab, HSK_ADAM_TAB_LEN, gdesc, grel};
+                              w.mcur, w.vcur, (int)st->step, cx.gen ? 1 : 0, cx.c, w.adam_tab, HSK_ADAM_TAB_LEN, cx.gdesc,
+                              cx.grel};
     else if (D % 2 == 0)
       lz.ucur = w.ucur;   // dense users in the item pass's launch: it reads the batch's rows from ucur
     hipEvent_t fwd_beg = nullptr, fwd_end = fork_ev;
@@ -1114,129 +1144,55 @@ static int hsk_run_step(hsk_bprmf_state* st, const hsk_ws& w_all, int set, bool 
       if (!fwd_beg || !fwd_end) return HSK_ERR_HIP;
       tm->beg[HSK_STAGE_FWD].push_back(fwd_beg);
       tm->end[HSK_STAGE_FWD].push_back(fwd_end);
-      timed_fwd_end = fwd_end;
+      *timed_fwd_end = fwd_end;
     }
-#define HSK_LAUNCH_FWD(LK)                                                                                          \
-  if (capturing)                                                                                                    \
-    hipLaunchKernelGGL((k_fwd_ugrad<V, NCH, FULL, R, LK>), dim3((unsigned)hsk_ceil_div(B, 4)), dim3(256), 0, stream,   \
-                       (const float*)st->user_emb, (const float*)st->item_emb, (const float*)st->item_bias,         \
-                       (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D, inv_bn, (float)st->ssm_log_adjust,  \
-                       w.g_s, w.dUb, w.loss_b, (const int*)nullptr, lz);                                            \
-  else                                                                                                              \
-    hipExtLaunchKernelGGL((k_fwd_ugrad<V, NCH, FULL, R, LK>), dim3((unsigned)hsk_ceil_div(B, 4)), dim3(256), 0, stream, \
-                          fwd_beg, fwd_end, 0, (const float*)st->user_emb, (const float*)st->item_emb,              \
-                          (const float*)st->item_bias, (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D,    \
-                          inv_bn, (float)st->ssm_log_adjust, w.g_s, w.dUb, w.loss_b, (const int*)nullptr, lz)
-    if (n_part > 1) {
-      // item-partitioned forward; the NEXT batch's user rows are brought up to date by leading workgroups of the same
-      // launch (pure VALU work beside a kernel that waits on the L2 / the fabric), see hsk_fwd_part.h
-      if constexpr (V == 4 && FULL) {
-        constexpr int RP = (V * NCH >= 16) ? 2 : HSK_FWD_PART_R;
-        hsk_ahead_args aa = {};
-        int n_ahead = 0;
-        static const int ahead_on = getenv("HSK_AHEAD") ? atoi(getenv("HSK_AHEAD")) : 1;
-        if (st->lazy_users && aux && ahead_on && !apart && (aux->pf_valid || aux->hint_valid)) {
-          const bool pf = aux->pf_valid;
-          aa = hsk_ahead_args{st->coo_user, pf ? aux->pf_order : aux->hint_order, pf ? aux->pf_start : aux->hint_start,
-                              (int)(pf ? aux->pf_batch : aux->hint_batch), w.stamp, w.claim, st->user_emb, st->m_user_emb,
-                              st->v_user_emb, st->user_bias, st->m_user_bias, st->v_user_bias, w.last_step, D,
-                              (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, gdesc, grel};
-          n_ahead = (int)hsk_align_up(hsk_ceil_div(aa.n, 4), 8);
-        }
-        const unsigned n_unit = 8u * (unsigned)hsk_ceil_div(hsk_ceil_div(B, 4), 8 / n_part);
-        // HSK_AHEAD_MIX=1: the ahead octets interleaved with the unit octets instead of leading (measured: 88 vs 86 us)
-        static const int ahead_mix = getenv("HSK_AHEAD_MIX") ? atoi(getenv("HSK_AHEAD_MIX")) : 0;
-        const int stride = (ahead_mix && n_ahead > 0) ? (int)(n_unit / 8) / (n_ahead / 8) : 0;
-        const hsk_part_args pa = {n_part, (int)st->n_items, n_ahead, stride};
-        const hsk_ride_fwd rf = (aux && aux->ride_fwd) ? *aux->ride_fwd : hsk_ride_fwd{};   // riding preparation phases
-        const unsigned grid = (unsigned)rf.n_total + (unsigned)n_ahead + n_unit;
-        // the overlapped gather loop (hsk_fwd_part.h: OVL) or the loop with a test per row: st->fwd_overlap (1 / -1) and
-        // HSK_FWD_OVERLAP (1 / 0) force it on / off, the state's field first; same bits either way
-        static const int ovl_env = getenv("HSK_FWD_OVERLAP") ? atoi(getenv("HSK_FWD_OVERLAP")) : -1;
-        const bool ovl = st->fwd_overlap ? st->fwd_overlap > 0 : ovl_env >= 0 ? ovl_env != 0 : HSK_FWD_OVERLAP_DEFAULT != 0;
-#define HSK_LAUNCH_FWD_PART_O(LK, GEN, OVL)                                                                         \
-  if (capturing)                                                                                                    \
-    hipLaunchKernelGGL((k_fwd_part<V, NCH, FULL, RP, LK, GEN, OVL>), dim3(grid), dim3(256), 0, stream,               \
-                       (const float*)st->user_emb, (const float*)st->item_emb, (const float*)st->item_bias,         \
-                       (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D, inv_bn, w.g_s, w.dUb, w.loss_b, lz,  \
-                       pa, aa, rf);                                                                                 \
-  else                                                                                                              \
-    hipExtLaunchKernelGGL((k_fwd_part<V, NCH, FULL, RP, LK, GEN, OVL>), dim3(grid), dim3(256), 0, stream, fwd_beg,   \
-                          fwd_end, 0, (const float*)st->user_emb, (const float*)st->item_emb,                        \
-                          (const float*)st->item_bias, (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D,    \
-                          inv_bn, w.g_s, w.dUb, w.loss_b, lz, pa, aa, rf)
-#define HSK_LAUNCH_FWD_PART(LK, GEN)                                                                                 \
-  if (ovl) { HSK_LAUNCH_FWD_PART_O(LK, GEN, true); } else { HSK_LAUNCH_FWD_PART_O(LK, GEN, false); }
-        if (st->loss_kind == HSK_LOSS_BCE) {
-          if (gen) { HSK_LAUNCH_FWD_PART(HSK_LOSS_BCE, true); } else { HSK_LAUNCH_FWD_PART(HSK_LOSS_BCE, false); }
-        } else {
-          if (gen) { HSK_LAUNCH_FWD_PART(HSK_LOSS_BPR, true); } else { HSK_LAUNCH_FWD_PART(HSK_LOSS_BPR, false); }
-        }
-#undef HSK_LAUNCH_FWD_PART
-#undef HSK_LAUNCH_FWD_PART_O
-        return HSK_OK;
-      } else {
-        hsk_set_error("internal: item-partitioned forward selected for dim %d", D);
-        return HSK_ERR_UNSUPPORTED;
-      }
-    }
+    if (cx.n_part > 1) return hsk_launch_fwd_part<V, NCH, FULL>(st, cx, stream, lz, apart, fwd_beg, fwd_end);
     // small batches: a workgroup per positive (hsk_fwd_small.h); the one-wave kernel would leave most SIMDs idle
     // and walk each positive's rows as a chain of memory latencies
-#define HSK_LAUNCH_FWD_WG(LK, NW)                                                                                   \
-  if (capturing)                                                                                                    \
-    hipLaunchKernelGGL((k_fwd_ugrad_wg<V, NCH, FULL, R, LK, NW>), dim3((unsigned)B), dim3(64 * NW),                    \
-                       (unsigned)(NW * (size_t)D * sizeof(float)), stream, (const float*)st->user_emb,              \
-                       (const float*)st->item_emb, (const float*)st->item_bias, (const int*)w.u32,                  \
-                       (const int*)w.it32, (int)B, (int)K, D, inv_bn, w.g_s, w.dUb, w.loss_b, lz);                   \
-  else                                                                                                              \
-    hipExtLaunchKernelGGL((k_fwd_ugrad_wg<V, NCH, FULL, R, LK, NW>), dim3((unsigned)B), dim3(64 * NW),                 \
-                          (unsigned)(NW * (size_t)D * sizeof(float)), stream, fwd_beg, fwd_end, 0,                   \
-                          (const float*)st->user_emb, (const float*)st->item_emb, (const float*)st->item_bias,      \
-                          (const int*)w.u32, (const int*)w.it32, (int)B, (int)K, D, inv_bn, w.g_s, w.dUb, w.loss_b, lz)
     // (also for very few columns: idle waves of the workgroup cost nothing at B = 128 and the kernel's loads come in two
     // rounds instead of four -- ml100k shape, K = 2: 13.8 -> 12.2 us per step; HSK_WG_MINK=9 restores the old rule)
-    static const int wg_min_k = getenv("HSK_WG_MINK") ? atoi(getenv("HSK_WG_MINK")) : 2;
+    static const int wg_min_k = hsk_env_int("HSK_WG_MINK", 2);
     const bool wg_fwd = B <= 1024 && st->loss_kind != HSK_LOSS_SSM && K >= wg_min_k;
     const bool wg8 = wg_fwd && K >= 33 && B <= 256;   // few, wide positives: 8 waves each
-    if (wg_fwd && st->loss_kind == HSK_LOSS_BCE) {
-      if (wg8) { HSK_LAUNCH_FWD_WG(HSK_LOSS_BCE, 8); } else { HSK_LAUNCH_FWD_WG(HSK_LOSS_BCE, 4); }
-    } else if (wg_fwd) {
-      if (wg8) { HSK_LAUNCH_FWD_WG(HSK_LOSS_BPR, 8); } else { HSK_LAUNCH_FWD_WG(HSK_LOSS_BPR, 4); }
-    } else if (st->loss_kind == HSK_LOSS_BCE) {
-      HSK_LAUNCH_FWD(HSK_LOSS_BCE);
-    } else if (st->loss_kind == HSK_LOSS_SSM) {
-      HSK_LAUNCH_FWD(HSK_LOSS_SSM);
-    } else {
-      HSK_LAUNCH_FWD(HSK_LOSS_BPR);
-    }
-#undef HSK_LAUNCH_FWD
-#undef HSK_LAUNCH_FWD_WG
-    return HSK_OK;
+    if (wg_fwd)   // (bpr and bce epilogues only)
+      return hsk_dispatch_loss<false>(st->loss_kind, [&](auto lk_) {
+        return hsk_dispatch_flags([&](auto wg8_) {
+          constexpr int NW = decltype(wg8_)::value ? 8 : 4;
+          hsk_launch_ev(k_fwd_ugrad_wg<V, NCH, FULL, R, decltype(lk_)::value, NW>, dim3((unsigned)B), dim3(64 * NW),
+                        (unsigned)(NW * (size_t)D * sizeof(float)), stream, cx.capturing, fwd_beg, fwd_end, st->user_emb,
+                        st->item_emb, st->item_bias, w.u32, w.it32, (int)B, (int)K, D, cx.inv_bn, w.g_s, w.dUb, w.loss_b,
+                        lz);
+          return HSK_OK;
+        }, wg8);
+      });
+    return hsk_dispatch_loss<true>(st->loss_kind, [&](auto lk_) {
+      hsk_launch_ev(k_fwd_ugrad<V, NCH, FULL, R, decltype(lk_)::value>, dim3((unsigned)hsk_ceil_div(B, 4)), dim3(256), 0,
+                    stream, cx.capturing, fwd_beg, fwd_end, st->user_emb, st->item_emb, st->item_bias, w.u32, w.it32, (int)B,
+                    (int)K, D, cx.inv_bn, (float)st->ssm_log_adjust, w.g_s, w.dUb, w.loss_b, (const int*)nullptr, lz);
+      return HSK_OK;
+    });
   });
-  if (rc) return rc;
-  HSK_LAUNCH_CHECK();
+}
 
-  if (late_fork) {
-    // the fork rides on the forward launch's own stop event: aux->ev_fork, or (timed step) the timing event
-    const bool fork_on_kernel = !capturing;
-    int prc = hsk_launch_prefetch(st, w_all, set, stream, fork_on_kernel, timed_fwd_end);
-    if (prc) return prc;
-  }
-
-  rc = hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
-    constexpr int V = decltype(v_)::value;
-    constexpr int NCH = decltype(n_)::value;
+// The updates of a step.  User update: the owners' rows (lazy: pending steps were replayed by the forward) or a dense
+// sweep over the table; + one workgroup for the loss reduction / global bias.  Even D: in the item pass's own launch,
+// unless the item or the user stage is timed -- then, as for odd D, the item pass and the user update are launched apart.
+static int hsk_launch_updates(hsk_bprmf_state* st, const hsk_step_ctx& cx, hipStream_t stream) {
+  const hsk_ws& w = cx.w;
+  const hsk_aux* aux = (const hsk_aux*)st->aux;
+  const int64_t B = cx.B, total = cx.B * cx.K;
+  const int U = (int)st->n_users, D = cx.D, n_part = cx.n_part;
+  const hsk_adamw_consts& c = cx.c;
+  return hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) -> int {
+    constexpr int V = decltype(v_)::value, NCH = decltype(n_)::value, R = (V * NCH >= 16) ? 2 : HSK_FWD_R;
     constexpr bool FULL = decltype(f_)::value;
-    constexpr int R = (V * NCH >= 16) ? 2 : HSK_FWD_R;
-    // user update: the owners' rows (lazy: pending steps were replayed by the forward) or a dense sweep over the
-    // table; + one workgroup for the loss reduction / global bias.  Even D: in the item pass's own launch.
-    const hsk_finish_args fin = {w.loss_b, (int)(B * n_part), inv_bn_d, st->loss_out, st->global_bias,
+    const hsk_finish_args fin = {w.loss_b, (int)(B * n_part), cx.inv_bn_d, st->loss_out, st->global_bias,
                                  st->m_global_bias, st->v_global_bias};   // partitioned forward: [n_part, B] partial terms
     const bool lazy = st->lazy_users != 0;
     const hsk_user_lazy_args ua = {st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, st->m_user_bias,
                                    st->v_user_bias, w.dUb, w.u32, w.owner, w.cnt, w.last_step, (int)B, D,
                                    (int)st->step, c, fin, w.dupcnt, w.duplist, lazy ? w.adam_tab : nullptr,
-                                   HSK_ADAM_TAB_LEN, w.ucur, w.mcur, w.vcur, lazy ? 0 : U, gdesc, grel, w.adam_tab,
+                                   HSK_ADAM_TAB_LEN, w.ucur, w.mcur, w.vcur, lazy ? 0 : U, cx.gdesc, cx.grel, w.adam_tab,
                                    HSK_ADAM_TAB_LEN, n_part};
     const bool timed_apart = st->timing && st->timing_now &&
                              (((st->timing_mask >> HSK_STAGE_ITEM) | (st->timing_mask >> HSK_STAGE_USER)) & 1);
@@ -1247,53 +1203,83 @@ static int hsk_run_step(hsk_bprmf_state* st, const hsk_ws& w_all, int set, bool 
       // At B = 4096 every kernel is within reach of its issue limit and the replay costs its ~10 us of VALU time
       // wherever it runs: measured 233 us per step with these workgroups in the item pass against 221 us with the
       // replay inside the forward, so large batches keep it there.
-      hsk_ahead_args aa = {};
-      static const int ahead_on = getenv("HSK_AHEAD") ? atoi(getenv("HSK_AHEAD")) : 1;
       // (huge catalogues with lazy item AdamW: the item launch is AdamW traffic on the touched rows, memory-bound with
       // idle VALUs, so the replay hides there as well)
-      if (lazy && aux && ahead_on && (hsk_pf_early(B) || st->lazy_items) && (aux->pf_valid || aux->hint_valid)) {
-        const bool pf = aux->pf_valid;
-        aa = hsk_ahead_args{st->coo_user, pf ? aux->pf_order : aux->hint_order, pf ? aux->pf_start : aux->hint_start,
-                            (int)(pf ? aux->pf_batch : aux->hint_batch), w.stamp, w.claim, st->user_emb, st->m_user_emb,
-                            st->v_user_emb, st->user_bias, st->m_user_bias, st->v_user_bias, w.last_step, D,
-                            (int)st->step, c, w.adam_tab, HSK_ADAM_TAB_LEN, gdesc, grel};
-      }
+      hsk_ahead_args aa = {};
+      if (hsk_pf_early(B) || st->lazy_items) hsk_make_ahead(st, cx, aux, &aa);
       // the item pass reads the user rows from ucur, the user blocks rewrite the table: independent -> one launch
-      hsk_launch_item_pass<V, NCH, FULL, R, true>(st, w, w.ucur, nullptr, (int)K, c, nullptr, nullptr, stream, total, &ua,
+      hsk_launch_item_pass<V, NCH, FULL, R, true>(st, w, w.ucur, nullptr, (int)cx.K, c, nullptr, nullptr, stream, total, &ua,
                                                   &aa, n_part, nullptr, nullptr, aux ? aux->ride_item : nullptr);
-    } else {
-      const bool from_ucur = lazy || D % 2 == 0;
-      HSK_STAGE(HSK_STAGE_ITEM, (hsk_launch_item_pass<V, NCH, FULL, R, true>(
-                                    st, w, from_ucur ? w.ucur : st->user_emb, from_ucur ? nullptr : w.u32, (int)K, c,
-                                    nullptr, nullptr, stream, total, nullptr, nullptr, n_part)));
-      if (n_part > 1) {   // partial gradient rows: the PART flavours (V == 4 && FULL by the partition rule)
-        if constexpr (V == 4 && FULL) {
-          const unsigned gl = (unsigned)hsk_ceil_div(B, 4) + 1, gd = (unsigned)hsk_ceil_div(U, 4) + 1;
-          if (lazy) {
-            if (gen) HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, true, true><<<gl, 256, 0, stream>>>(ua)));
-            else     HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, false, true><<<gl, 256, 0, stream>>>(ua)));
-          } else {
-            if (gen) HSK_STAGE(HSK_STAGE_USER, (k_user_update_dense<V, NCH, FULL, true, true><<<gd, 256, 0, stream>>>(ua)));
-            else     HSK_STAGE(HSK_STAGE_USER, (k_user_update_dense<V, NCH, FULL, false, true><<<gd, 256, 0, stream>>>(ua)));
-          }
-        }
-      } else if (lazy) {
-        if (gen)
-          HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, true><<<(unsigned)hsk_ceil_div(B, 4) + 1, 256, 0, stream>>>(ua)));
-        else
-          HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, false><<<(unsigned)hsk_ceil_div(B, 4) + 1, 256, 0, stream>>>(ua)));
-      } else {
-        if (gen)
-          HSK_STAGE(HSK_STAGE_USER, (k_user_update_dense<V, NCH, FULL, true><<<(unsigned)hsk_ceil_div(U, 4) + 1, 256, 0, stream>>>(ua)));
-        else
-          HSK_STAGE(HSK_STAGE_USER, (k_user_update_dense<V, NCH, FULL, false><<<(unsigned)hsk_ceil_div(U, 4) + 1, 256, 0, stream>>>(ua)));
-      }
+      return HSK_OK;
     }
-    return HSK_OK;
+    const bool from_ucur = lazy || D % 2 == 0;
+    HSK_STAGE(HSK_STAGE_ITEM, (hsk_launch_item_pass<V, NCH, FULL, R, true>(
+                                  st, w, from_ucur ? w.ucur : st->user_emb, from_ucur ? nullptr : w.u32, (int)cx.K, c,
+                                  nullptr, nullptr, stream, total, nullptr, nullptr, n_part)));
+    // partial gradient rows: the PART flavours (V == 4 && FULL by the partition rule)
+    return hsk_dispatch_flags([&](auto lazy_, auto gen_, auto part_) {
+      constexpr bool GEN = decltype(gen_)::value, PART = decltype(part_)::value;
+      if constexpr (!PART || (V == 4 && FULL)) {
+        if constexpr (decltype(lazy_)::value)
+          HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, GEN, PART>
+                                     <<<(unsigned)hsk_ceil_div(B, 4) + 1, 256, 0, stream>>>(ua)));
+        else
+          HSK_STAGE(HSK_STAGE_USER, (k_user_update_dense<V, NCH, FULL, GEN, PART>
+                                     <<<(unsigned)hsk_ceil_div(U, 4) + 1, 256, 0, stream>>>(ua)));
+      }
+      return HSK_OK;
+    }, lazy, cx.gen, n_part > 1);
   });
+}
+
+// stages after prep filled u32 / it32 / owner / cnt of `w` (and, with sorted == true, the item sort too)
+// n_part > 1: batch rows in the partitioned layout (the positive in n_part columns) -> item-partitioned forward
+// slot: the batch's slot inside the set (grouped preparation)
+static int hsk_run_step(hsk_bprmf_state* st, const hsk_ws& w_all, int set, bool sorted, int64_t B, int64_t K_real,
+                        hipStream_t stream, int n_part = 1, int slot = 0) {
+  hsk_aux* aux = (hsk_aux*)st->aux;
+  st->step += 1;
+  const bool capturing = aux && aux->g_desc;
+  const double inv_bn_d = hsk_loss_norm(st->loss_kind, (double)B, (double)K_real);
+  const hsk_step_ctx cx = {hsk_select(w_all, set, slot), B, hsk_part_cols(K_real, n_part), (int)st->dim, n_part,
+                           hsk_make_adamw_consts(st->lr, st->beta1, st->beta2, st->eps, st->wd, st->step, st->opt_kind),
+                           inv_bn_d, (float)inv_bn_d, st->opt_kind != HSK_OPT_ADAMW, capturing,
+                           capturing ? aux->g_desc : nullptr, capturing ? aux->g_rel : 0};
+  const hsk_ws& w = cx.w;
+  const int64_t total = B * cx.K;
+  if (aux) {
+    aux->cur_set = aux->last_set = set;
+    aux->cur_slot = aux->last_slot = slot;
+  }
+  if (!sorted) {
+    int src = hsk_launch_sort(st, w, total, stream);
+    if (src) return src;
+  }
+  if (st->lazy_items) {
+    HSK_STAGE(HSK_STAGE_ITEM, hsk_launch_item_catch_up(st, w, stream, (unsigned)std::min<int64_t>(st->n_items, total), false,
+                                                       st->step, cx.c, cx.gdesc, cx.grel));
+    HSK_LAUNCH_CHECK();
+  }
+  if (hsk_pf_early(B)) {
+    int prc = hsk_launch_prefetch(st, w_all, set, stream);
+    if (prc) return prc;
+  }
+  // late fork: the fork event is the forward kernel's own completion signal (an ordinary event record in a capture)
+  const bool late_fork = !hsk_pf_early(B) && hsk_prefetch_wanted(st);
+  hipEvent_t timed_fwd_end = nullptr;   // a timed step: the forward launch's stop event doubles as the fork event
+  int rc = hsk_launch_forward(st, cx, stream, (late_fork && !cx.capturing) ? aux->ev_fork : nullptr, &timed_fwd_end);
   if (rc) return rc;
   HSK_LAUNCH_CHECK();
-  if (!capturing && (st->lazy_users || st->lazy_items)) {
+  if (late_fork) {
+    // the fork rides on the forward launch's own stop event: aux->ev_fork, or (timed step) the timing event
+    const bool fork_on_kernel = !cx.capturing;
+    int prc = hsk_launch_prefetch(st, w_all, set, stream, fork_on_kernel, timed_fwd_end);
+    if (prc) return prc;
+  }
+  rc = hsk_launch_updates(st, cx, stream);
+  if (rc) return rc;
+  HSK_LAUNCH_CHECK();
+  if (!cx.capturing && (st->lazy_users || st->lazy_items)) {
     int frc = hsk_periodic_flush(st, w, stream, st->step - 1, (double)B, (double)(B * K_real));
     if (frc) return frc;
   }
@@ -1346,7 +1332,7 @@ static bool hsk_pipe_plan(const hsk_bprmf_state* st, int64_t batch, int64_t n_ne
 
 // HSK_PIPE=0 / hsk_bprmf_set_pipeline(0): the side-stream prefetch everywhere (A/B runs, and the reference the
 // bit-equality tests hold the pipeline to)
-static int hsk_pipe_switch = getenv("HSK_PIPE") ? atoi(getenv("HSK_PIPE")) : 1;
+static int hsk_pipe_switch = hsk_env_int("HSK_PIPE", 1);
 extern "C" void hsk_bprmf_set_pipeline(int on) { hsk_pipe_switch = on ? 1 : 0; }
 
 static bool hsk_pipe_eligible(const hsk_bprmf_state* st, int64_t batch, int64_t n_neg) {
@@ -1456,7 +1442,7 @@ static int hsk_pipe_step(hsk_bprmf_state* st, const hsk_ws& w_all, const hsk_bat
   }
   // HSK_PIPE_ALONE=1 (experiments): nothing rides -- every phase of the step's batch as a launch of its own in front of it
   // (a timeline then shows the forward, the item/user launch and the five phases each by itself)
-  static const int alone = getenv("HSK_PIPE_ALONE") ? atoi(getenv("HSK_PIPE_ALONE")) : 0;
+  static const int alone = hsk_env_int("HSK_PIPE_ALONE", 0);
   const int sc = slot_of[0], s1 = alone ? -1 : slot_of[1], s2 = alone ? -1 : slot_of[2];
   if (alone) {
     const hsk_ws w = hsk_select(w_all, sc);
@@ -1478,7 +1464,7 @@ static int hsk_pipe_step(hsk_bprmf_state* st, const hsk_ws& w_all, const hsk_bat
   }
   // HSK_PIPE_SOLO=mask (experiments: what a rider costs its host launch): 1 sampler, 2 histogram, 4 row scan, 8 scatter,
   // 16 bucket -- that phase (and the ones in front of it) as a launch of its own in front of the step instead of riding
-  static const int solo = getenv("HSK_PIPE_SOLO") ? atoi(getenv("HSK_PIPE_SOLO")) : 0;
+  static const int solo = hsk_env_int("HSK_PIPE_SOLO", 0);
   if (solo) {
     const int upto[3] = {(solo & 16) ? HSK_PIPE_B : 0, (solo & 8) ? HSK_PIPE_C : (solo & 4) ? HSK_PIPE_R : 0,
                          (solo & 2) ? HSK_PIPE_H : (solo & 1) ? HSK_PIPE_S : 0};
@@ -1517,7 +1503,7 @@ static int hsk_pipe_step(hsk_bprmf_state* st, const hsk_ws& w_all, const hsk_bat
     const hsk_ws w2 = hsk_select(w_all, s2);
     const hsk_aux::pipe_slot& b = a->pipe[s2];
     if (b.stage == HSK_PIPE_NONE) {
-      static const int s_per_wave = getenv("HSK_PIPE_S_PER_WAVE") ? std::min(64, std::max(1, atoi(getenv("HSK_PIPE_S_PER_WAVE")))) : 8;
+      static const int s_per_wave = std::min(64, std::max(1, hsk_env_int("HSK_PIPE_S_PER_WAVE", 8)));
       rf.S = hsk_ride_sample{(int)hsk_ceil_div(b.batch, 4 * s_per_wave), st->coo_user, st->coo_item, b.order, (long long)b.start,
                              (int)b.batch, (int)b.n_neg, st->csr_indptr, st->csr_indices, (int)st->n_items, st->seed,
                              (uint64_t)b.step, w2.u32, w2.it32, w2.owner, w2.cnt, st->status,
@@ -1560,7 +1546,7 @@ extern "C" int hsk_bprmf_train_step(hsk_bprmf_state* st, const int64_t* u_idx, c
   hipStream_t stream = (hipStream_t)stream_;
   hsk_ws w = hsk_carve_st(st);
   const int64_t total = batch * n_cols;
-  st->timing_now = st->timing && (st->timing_every <= 1 || ((st->step + 1) % st->timing_every) == 0);
+  hsk_timing_arm(st);
   if ((rc = hsk_pipe_reset(st, w, stream))) return rc;
   if ((rc = hsk_discard_prefetch(st, w, stream))) return rc;
   const int set = st->aux ? (((hsk_aux*)st->aux)->cur_set ^ 1) : 0;
@@ -1585,7 +1571,7 @@ extern "C" int hsk_bprmf_train_step_sampled(hsk_bprmf_state* st, const int64_t* 
   hipStream_t stream = (hipStream_t)stream_;
   hsk_ws w = hsk_carve_st(st);
   // the RNG stream id is the index of the step about to be taken: every step draws fresh negatives
-  st->timing_now = st->timing && (st->timing_every <= 1 || ((st->step + 1) % st->timing_every) == 0);
+  hsk_timing_arm(st);
   hsk_aux* aux = (hsk_aux*)st->aux;
   const int n_part = hsk_part_rule_st(st, batch, n_neg);
   if ((rc = hsk_pipe_reset(st, w, stream))) return rc;
@@ -1640,7 +1626,7 @@ static hsk_bprmf_state hsk_graph_key(const hsk_bprmf_state* st) {
 }
 
 static int64_t hsk_graph_chunk(const hsk_bprmf_state* st) {
-  static const int env = getenv("HSK_GRAPH") ? atoi(getenv("HSK_GRAPH")) : 1;
+  static const int env = hsk_env_int("HSK_GRAPH", 1);
   if (!env || st->graph_chunk < 0) return 0;
   const hsk_aux* a = (const hsk_aux*)st->aux;
   if (!a || a->graph_broken) return 0;
@@ -1648,7 +1634,7 @@ static int64_t hsk_graph_chunk(const hsk_bprmf_state* st) {
   if (st->dim % 2 != 0) return 0;                         // the merged item + user launch carries the descriptor
   if ((st->lazy_users || st->lazy_items) && !hsk_adam_tab_saturates(st)) return 0;
   if (st->step + 2 * HSK_GRAPH_DEFAULT_CHUNK >= HSK_ADAM_TAB_LEN && !hsk_adam_tab_saturates(st)) return 0;
-  static const int env_chunk = getenv("HSK_GRAPH_CHUNK") ? atoi(getenv("HSK_GRAPH_CHUNK")) : 0;   // experiments
+  static const int env_chunk = hsk_env_int("HSK_GRAPH_CHUNK", 0);   // experiments
   return st->graph_chunk > 0 ? st->graph_chunk : env_chunk > 1 ? env_chunk : HSK_GRAPH_DEFAULT_CHUNK;
 }
 
@@ -1799,7 +1785,7 @@ extern "C" int hsk_bprmf_train_steps(hsk_bprmf_state* st, const int64_t* order, 
       cur.step = st->step;
       n1.step = st->step + 1;
       n2.step = st->step + 2;
-      st->timing_now = st->timing && (st->timing_every <= 1 || ((st->step + 1) % st->timing_every) == 0);
+      hsk_timing_arm(st);
       if ((rc = hsk_pipe_step(st, w, cur, n1, n2, stream))) return rc;
     }
     aux->tail_valid = false;
@@ -1846,7 +1832,7 @@ extern "C" int hsk_bprmf_train_steps(hsk_bprmf_state* st, const int64_t* order, 
         ++gi;
       }
       if (!exec) {
-        static const int dbg = getenv("HSK_DEBUG_GRAPH") ? atoi(getenv("HSK_DEBUG_GRAPH")) : 0;
+        static const int dbg = hsk_env_int("HSK_DEBUG_GRAPH", 0);
         if (dbg) fprintf(stderr, "hsk: capturing %lld steps (batch %lld, %zu cached)\n", (long long)n, (long long)batch, aux->graphs.size());
         if ((rc = hsk_capture_steps(st, w, n, batch, n_neg, set0, &exec))) {
           aux->graph_broken = true;   // eager launches from here on (the error text stays available)

@@ -517,7 +517,7 @@ static int hsk_shard_step_enqueue(hsk_bprmf_shard* sh, hsk_shard_rt* rt, const i
   // just trained on were rewritten by the update in front and are skipped as current.  Measured on one rank at the
   // ml10m shape, three alternations on one box: 286-288 us per step without, 295-300 with -- the communication stream's
   // chain (exchange + update + replay) then outlasts the item pass it runs beside, and the join waits for it.
-  static const int ahead_on = getenv("HSK_SHARD_AHEAD") ? atoi(getenv("HSK_SHARD_AHEAD")) : 0;
+  static const int ahead_on = hsk_env_int("HSK_SHARD_AHEAD", 0);
   if (rt->pf_valid && ahead_on) {
     HSK_HIP(hipStreamWaitEvent(rt->cs, rt->ev_ready, 0));
     if ((rc = hsk_shard_catch_up_rows(sh, rt->pf_set, st->step + 1, rt->cs, false))) return rc;

@@ -2,6 +2,7 @@
 // training kernels.  One wavefront owns one row: lane l holds elements (c*64 + l)*V .. +V of chunk c.
 #pragma once
 #include "hsk_common.h"
+#include <hip/hip_ext.h>
 #include <type_traits>
 
 #define HSK_OWNER_NONE 0x7fffffff
@@ -42,6 +43,38 @@ static int hsk_dispatch_dim(int64_t D, F&& f) {
 #undef HSK_CASE
   hsk_set_error("internal: no kernel for dim %lld", (long long)D);
   return HSK_ERR_UNSUPPORTED;
+}
+
+// runtime booleans -> template flags: f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...), the first flag first.
+// f is instantiated for EVERY combination, so a combination without a kernel needs an `if constexpr` inside f.
+template <typename F>
+static int hsk_dispatch_flags(F&& f) { return f(); }
+template <typename F, typename... Bs>
+static int hsk_dispatch_flags(F&& f, bool b0, Bs... bs) {
+  auto bound = [&](auto c0) { return hsk_dispatch_flags([&](auto... cs) { return f(c0, cs...); }, bs...); };
+  return b0 ? bound(std::true_type{}) : bound(std::false_type{});
+}
+
+// loss kind -> f(std::integral_constant<int, HSK_LOSS_*>{}).  WITH_SSM = false: for kernels that carry the bpr and bce
+// epilogues only (every other kind takes the bpr one, the callers keep sampled softmax away from them)
+template <bool WITH_SSM, typename F>
+static int hsk_dispatch_loss(int kind, F&& f) {
+  if (kind == HSK_LOSS_BCE) return f(std::integral_constant<int, HSK_LOSS_BCE>{});
+  if constexpr (WITH_SSM)
+    if (kind == HSK_LOSS_SSM) return f(std::integral_constant<int, HSK_LOSS_SSM>{});
+  return f(std::integral_constant<int, HSK_LOSS_BPR>{});
+}
+
+// One launch that may carry events: hipExtLaunchKernelGGL with `beg` / `end` (NULL: none) as the dispatch's own start /
+// stop timestamps, or, capturing, an ordinary launch.  Every kernel argument is written out, defaults included.
+template <typename... KArgs, typename... Args>
+static void hsk_launch_ev(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream,
+                          bool capturing, hipEvent_t beg, hipEvent_t end, const Args&... args) {
+  static_assert(sizeof...(KArgs) == sizeof...(Args), "hsk_launch_ev: pass every kernel argument, defaults included");
+  if (capturing)
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, static_cast<KArgs>(args)...);
+  else
+    hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, beg, end, 0, static_cast<KArgs>(args)...);
 }
 
 // ---------------------------------------------------------------------------------------------

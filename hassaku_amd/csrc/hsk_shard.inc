@@ -612,22 +612,9 @@ static int hsk_shard_catch_up_rows(hsk_bprmf_shard* sh, int set, int64_t step, h
   hsk_bprmf_state* st = &sh->base;
   const hsk_ws w = hsk_select(hsk_carve_st(st), set);
   const hsk_shard_ws x = hsk_shard_carve(sh->shard_ws, st->max_batch, st->max_cols, sh->capacity, sh->entry_cap);
-  const int C = (int)sh->capacity, D = (int)st->dim;
   const hsk_adamw_consts c = hsk_make_adamw_consts(st->lr, st->beta1, st->beta2, st->eps, st->wd, step, st->opt_kind);
-  const bool gen = st->opt_kind != HSK_OPT_ADAMW;
-#define HSK_CATCH_UP(VV, GEN)                                                                                        \
-  k_user_catch_up<VV, GEN><<<(unsigned)C, 256, 0, stream>>>(st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, \
-                                                            st->m_user_bias, st->v_user_bias, x.req[set], w.owner,     \
-                                                            w.last_step, C, D, (int)step, c, w.adam_tab,               \
-                                                            HSK_ADAM_TAB_LEN, register_dups ? w.dupcnt : nullptr,       \
-                                                            register_dups ? w.duplist : nullptr, x.ovf[set], x.poison, \
-                                                            opens ? 1 : 0)
-  if (D % 2 == 0) {
-    if (gen) HSK_CATCH_UP(2, true); else HSK_CATCH_UP(2, false);
-  } else {
-    if (gen) HSK_CATCH_UP(1, true); else HSK_CATCH_UP(1, false);
-  }
-#undef HSK_CATCH_UP
+  hsk_launch_user_catch_up(st, w, stream, x.req[set], (int)sh->capacity, step, c, register_dups ? w.dupcnt : nullptr,
+                           register_dups ? w.duplist : nullptr, x.ovf[set], x.poison, opens ? 1 : 0);
   HSK_LAUNCH_CHECK();
   return HSK_OK;
 }
@@ -645,7 +632,7 @@ extern "C" int hsk_shard_pack(hsk_bprmf_shard* sh, int64_t batch, int64_t n_neg,
     sh->cur_set = set_;
   }
   HSK_SHARD_BEGIN(HSK_SHARD_IDLE, "hsk_shard_pack");
-  st->timing_now = st->timing && (st->timing_every <= 1 || ((st->step + 1) % st->timing_every) == 0);
+  hsk_timing_arm(st);
   if ((rc = hsk_shard_catch_up_rows(sh, set, st->step + 1, stream, true, true))) return rc;
   rc = hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
     constexpr int V = decltype(v_)::value;
@@ -669,18 +656,7 @@ extern "C" int hsk_shard_pos_scores(hsk_bprmf_shard* sh, hsk_stream_t stream_) {
     const unsigned nblk = (unsigned)std::min<int64_t>(st->n_items, sh->entry_cap);
     // (rows of 1024 floats and more, 16-byte aligned: four floats per thread -- a 4 KB row in ONE pass of the workgroup
     // instead of two dependent ones)
-#define HSK_ITEM_CATCH_UP(VV, GEN)                                                                                   \
-  k_item_catch_up<VV, GEN><<<nblk, 256, 0, stream>>>(st->item_emb, st->m_item_emb, st->v_item_emb, st->item_bias,    \
-                                                     st->m_item_bias, st->v_item_bias, w.touched, w.n_touched,        \
-                                                     w.last_step_i, D, (int)st->step + 1, c, w.adam_tab,              \
-                                                     HSK_ADAM_TAB_LEN, nullptr, 0, w.pend, x.ovf[set], x.poison)
-    const bool wide_rows = D % 4 == 0 && D >= 1024;
-    if (st->opt_kind != HSK_OPT_ADAMW) {
-      if (wide_rows) HSK_ITEM_CATCH_UP(4, true); else HSK_ITEM_CATCH_UP(2, true);
-    } else {
-      if (wide_rows) HSK_ITEM_CATCH_UP(4, false); else HSK_ITEM_CATCH_UP(2, false);
-    }
-#undef HSK_ITEM_CATCH_UP
+    hsk_launch_item_catch_up(st, w, stream, nblk, D % 4 == 0 && D >= 1024, st->step + 1, c, nullptr, 0, x.ovf[set], x.poison);
     HSK_LAUNCH_CHECK();
   }
   rc = hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
@@ -707,16 +683,13 @@ extern "C" int hsk_shard_forward(hsk_bprmf_shard* sh, hsk_stream_t stream_) {
     constexpr int NCH = decltype(n_)::value;
     constexpr bool FULL = decltype(f_)::value;
     constexpr int R = (V * NCH >= 16) ? 2 : 4;
-#define HSK_SHARD_FWD(LK)                                                                                            \
-  HSK_STAGE(HSK_STAGE_FWD, (k_shard_fwd<V, NCH, FULL, R, LK><<<(unsigned)hsk_ceil_div(G, 4), 256, 0, stream>>>(          \
-                               sh->rows_all, st->item_emb, st->item_bias, x.slot_of_b[set], x.pos_local[set], x.offs[set], \
-                               w.it32, sh->s0, (int)G, D, inv_bn, (float)st->ssm_log_adjust, w.g_s, sh->dU_all, sh->gsum,  \
-                               w.loss_b, sh->ssm_send)))
-    if (st->loss_kind == HSK_LOSS_BCE) HSK_SHARD_FWD(HSK_LOSS_BCE);
-    else if (st->loss_kind == HSK_LOSS_SSM) HSK_SHARD_FWD(HSK_LOSS_SSM);
-    else HSK_SHARD_FWD(HSK_LOSS_BPR);
-#undef HSK_SHARD_FWD
-    return HSK_OK;
+    return hsk_dispatch_loss<true>(st->loss_kind, [&](auto lk_) {
+      HSK_STAGE(HSK_STAGE_FWD, (k_shard_fwd<V, NCH, FULL, R, decltype(lk_)::value><<<(unsigned)hsk_ceil_div(G, 4), 256, 0, stream>>>(
+                                   sh->rows_all, st->item_emb, st->item_bias, x.slot_of_b[set], x.pos_local[set], x.offs[set],
+                                   w.it32, sh->s0, (int)G, D, inv_bn, (float)st->ssm_log_adjust, w.g_s, sh->dU_all, sh->gsum,
+                                   w.loss_b, sh->ssm_send)));
+      return HSK_OK;
+    });
   });
   if (rc) return rc;
   HSK_LAUNCH_CHECK();
@@ -784,7 +757,6 @@ static int hsk_shard_apply_users_impl(hsk_bprmf_shard* sh, hsk_stream_t stream_,
   st->step += 1;
   const hsk_adamw_consts c = hsk_make_adamw_consts(st->lr, st->beta1, st->beta2, st->eps, st->wd, st->step, st->opt_kind);
   const double inv_bn_d = hsk_loss_norm(st->loss_kind, (double)G, (double)K);
-  const bool gen = st->opt_kind != HSK_OPT_ADAMW;
   rc = hsk_dispatch_dim(D, [&](auto v_, auto n_, auto f_) {
     constexpr int V = decltype(v_)::value;
     constexpr int NCH = decltype(n_)::value;
@@ -796,12 +768,11 @@ static int hsk_shard_apply_users_impl(hsk_bprmf_shard* sh, hsk_stream_t stream_,
     const hsk_user_lazy_args ua = {st->user_emb, st->m_user_emb, st->v_user_emb, st->user_bias, st->m_user_bias,
                                    st->v_user_bias, sh->grads_mine, x.req[set], w.owner, w.cnt, w.last_step, C, D,
                                    (int)st->step, c, fin, w.dupcnt, w.duplist, nullptr, 0, nullptr, nullptr, nullptr};
-#define HSK_USER_LAZY(GEN) \
-  HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, GEN><<<(unsigned)hsk_ceil_div(C, 4) + 1, 256, 0, stream>>>( \
-                                ua, x.ovf[set], x.poison)))
-    if (gen) HSK_USER_LAZY(true); else HSK_USER_LAZY(false);
-#undef HSK_USER_LAZY
-    return HSK_OK;
+    return hsk_dispatch_flags([&](auto gen_) {
+      HSK_STAGE(HSK_STAGE_USER, (k_user_update_lazy<V, NCH, FULL, decltype(gen_)::value>
+                                 <<<(unsigned)hsk_ceil_div(C, 4) + 1, 256, 0, stream>>>(ua, x.ovf[set], x.poison)));
+      return HSK_OK;
+    }, st->opt_kind != HSK_OPT_ADAMW);
   });
   if (rc) return rc;
   HSK_LAUNCH_CHECK();
