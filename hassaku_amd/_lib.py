@@ -204,6 +204,8 @@ SIGNATURES = {
                                       c_void_p]),
     'hsk_svd_score_rows': (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    'hsk_als_solve_f64': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                  c_int64, c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

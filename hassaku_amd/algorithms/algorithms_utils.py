@@ -14,8 +14,13 @@ that resolves a slot by name -- run_experiment.py, the experiment helpers -- tak
 contents).  `NeuralAlgorithmsEnum` holds `dmf`, trained by the Trainer like the first family;
 `EXPERIMENT_ALGORITHM_NAMES` = `CLI_ALGORITHM_NAMES` + ('dmf',).  `TagAlgorithmsEnum` holds `ecf`, trained by the
 Trainer too, on a dataset that carries the item x tag matrix; `RUNNABLE_ALGORITHM_NAMES` =
-`EXPERIMENT_ALGORITHM_NAMES` + ('ecf',) is what run_experiment.py offers.  Callers use only a slot's `.name` and
-`.value`.
+`EXPERIMENT_ALGORITHM_NAMES` + ('ecf',).  Callers use only a slot's `.name` and `.value`.
+
+`WeightedFactorAlgorithmsEnum` holds `als` (implicit-feedback alternating least squares, fitted on the train CSR like
+the other closed-form models).  It is not among the families `AlgorithmsEnum` looks through: `AlgorithmsEnum['als']`
+raises KeyError as it always has, and `RUNNABLE_ALGORITHM_NAMES` keeps its contents.  `algorithm_by_name(name)`
+resolves every slot, the new family included, and `OFFERED_ALGORITHM_NAMES` = `RUNNABLE_ALGORITHM_NAMES` + ('als',)
+is what run_experiment.py offers.
 """
 from enum import Enum, EnumMeta
 
@@ -23,7 +28,7 @@ from hassaku_amd.algorithms.ecf_alg import ECF
 from hassaku_amd.algorithms.graph_algs import P3alpha
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN
 from hassaku_amd.algorithms.linear_algs import EASE
-from hassaku_amd.algorithms.mf_algs import SVDAlgorithm
+from hassaku_amd.algorithms.mf_algs import AlternatingLeastSquare, SVDAlgorithm
 from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
 from hassaku_amd.algorithms.proto_alg import ACF, IProtoMF, UIProtoMF, UProtoMF
 from hassaku_amd.algorithms.sgd_alg import SGDBaseline, SGDMatrixFactorization
@@ -52,6 +57,10 @@ class NeuralAlgorithmsEnum(Enum):
 
 class TagAlgorithmsEnum(Enum):
     ecf = ECF
+
+
+class WeightedFactorAlgorithmsEnum(Enum):   # reached through algorithm_by_name(), not through AlgorithmsEnum
+    als = AlternatingLeastSquare
 
 
 _OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum, GraphAlgorithmsEnum, FactorAlgorithmsEnum,
@@ -95,3 +104,12 @@ REGISTERED_ALGORITHM_NAMES = ALL_ALGORITHM_NAMES + tuple(m.name for m in GraphAl
 CLI_ALGORITHM_NAMES = REGISTERED_ALGORITHM_NAMES + tuple(m.name for m in FactorAlgorithmsEnum)
 EXPERIMENT_ALGORITHM_NAMES = CLI_ALGORITHM_NAMES + tuple(m.name for m in NeuralAlgorithmsEnum)
 RUNNABLE_ALGORITHM_NAMES = EXPERIMENT_ALGORITHM_NAMES + tuple(m.name for m in TagAlgorithmsEnum)
+OFFERED_ALGORITHM_NAMES = RUNNABLE_ALGORITHM_NAMES + tuple(m.name for m in WeightedFactorAlgorithmsEnum)
+
+
+def algorithm_by_name(name: str):
+    """The slot called `name`: `AlgorithmsEnum[name]`, or the member of `WeightedFactorAlgorithmsEnum`."""
+    try:
+        return AlgorithmsEnum[name]
+    except KeyError:
+        return WeightedFactorAlgorithmsEnum[name]

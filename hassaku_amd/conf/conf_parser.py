@@ -66,7 +66,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
     from hassaku_amd.algorithms.graph_algs import P3alpha, validate_p3alpha_conf
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
     from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
-    from hassaku_amd.algorithms.mf_algs import SVDAlgorithm, validate_svd_conf
+    from hassaku_amd.algorithms.mf_algs import (AlternatingLeastSquare, SVDAlgorithm, validate_als_conf,
+                                                validate_svd_conf)
     from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
     from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 
@@ -80,6 +81,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
         validate_p3alpha_conf(conf)
     elif issubclass(alg.value, SVDAlgorithm):
         validate_svd_conf(conf)
+    elif issubclass(alg.value, AlternatingLeastSquare):
+        validate_als_conf(conf)
     elif issubclass(alg.value, DeepMatrixFactorization):
         validate_dmf_conf(conf)   # its own keys; the SGD defaults below apply as for any trained model
     elif issubclass(alg.value, ECF):

@@ -1283,9 +1283,11 @@ def svd_gram_ws_bytes(n: int, b: int) -> int:
     return int(_lib.load().hsk_svd_gram_ws_bytes(int(n), int(b)))
 
 
-def svd_gram(A: torch.Tensor, B: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+def svd_gram(A: torch.Tensor, B: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp64 [b, b]: A^T B (B = A if not given) of two [n, b] blocks on the fp64 matrix cores; bitwise equal from call
-    to call.  ws: a contiguous fp64 workspace of at least svd_gram_ws_bytes(n, b) bytes (allocated if not given)."""
+    to call.  ws: a contiguous fp64 workspace of at least svd_gram_ws_bytes(n, b) bytes (allocated if not given);
+    out: a contiguous fp64 [b, b] tensor to write (allocated if not given)."""
     _lib.require_gpu()
     lib = _lib.load()
     B = A if B is None else B
@@ -1299,7 +1301,8 @@ def svd_gram(A: torch.Tensor, B: Optional[torch.Tensor] = None, ws: Optional[tor
     _chk(ws, torch.float64, 'ws')
     if ws.numel() * 8 < need or ws.data_ptr() % 16:
         raise ValueError(f'ws holds {ws.numel() * 8} bytes, svd_gram needs {need}, 16-byte aligned')
-    H = torch.empty((b, b), dtype=torch.float64, device=A.device)
+    H = torch.empty((b, b), dtype=torch.float64, device=A.device) if out is None else out
+    _chk(H, torch.float64, 'out', (b, b))
     _lib.check(lib.hsk_svd_gram_f64(_p(A), lda, _p(B), ldb, n, b, _p(H), b, _p(ws), ws.numel() * 8, _stream()),
                'hsk_svd_gram_f64')
     return H
@@ -1355,4 +1358,43 @@ def svd_score_rows(users: torch.Tensor, UF: torch.Tensor, IF: torch.Tensor, excl
     out, status = _score_out(out, R, n_items, users.device), _status_word(status, users.device)
     _lib.check(lib.hsk_svd_score_rows(_p(users), R, n_users, _p(UF), ldu, _p(IF), ldi, n_items, k, _p(ep), _p(ei),
                                       _p(out), out.shape[1], _p(status), _stream()), 'hsk_svd_score_rows')
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# ALS (hsk_als.hip)
+# ---------------------------------------------------------------------------------------------------
+ALS_MAX_FACTORS = 128    # HSK_ALS_MAX_FACTORS: more factors are refused by the library (error code), not here
+
+
+def als_solve(csr, Y: torch.Tensor, G: torch.Tensor, alpha: float, reg: float, order: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp64 [n_rows, k]: one ALS half-sweep, row r = (G + reg I + (alpha - 1) sum y_i y_i^T)^-1 (alpha sum y_i) over
+    the column ids i of row r of the binary CSR, by Cholesky; a row without entries is exactly 0.  csr: (indptr int64
+    [n_rows + 1], indices int32, n_cols); Y [n_cols, k] the other side's factors, G [k, k] = Y^T Y (svd_gram); order:
+    int32 [n_rows], a permutation of the rows (the issue order; it changes no result).  status collects
+    HSK_STATUS_BAD_INDEX (1: a column id out of range, skipped) and HSK_STATUS_NOT_SPD (8: the row is zeros)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    ptr, idx, n_cols = csr
+    n_rows = ptr.numel() - 1
+    _chk(ptr, torch.int64, 'indptr', (n_rows + 1,))
+    _chk(idx, torch.int32, 'indices')
+    yr, k, ldy = _svd_dense(Y, 'Y')
+    gr, gk, ldg = _svd_dense(G, 'G', even=False)
+    if yr != n_cols or n_rows < 1:
+        raise ValueError(f'Y has {yr} rows, the CSR {n_cols} columns and {n_rows} rows')
+    if (gr, gk) != (k, k):
+        raise ValueError(f'G has shape {tuple(G.shape)}, expected ({k}, {k})')
+    _chk(order, torch.int32, 'order', (n_rows,), optional=True)
+    if out is None:
+        out = svd_empty(n_rows, k, Y.device)
+    orr, ob, ldo = _svd_dense(out, 'out')
+    if (orr, ob) != (n_rows, k):
+        raise ValueError(f'out has shape {tuple(out.shape)}, expected ({n_rows}, {k})')
+    status = _status_word(status, Y.device)
+    _chk(status, torch.int32, 'status', (1,))
+    _lib.check(lib.hsk_als_solve_f64(_p(ptr), _p(idx), n_rows, n_cols, _p(order), _p(Y), ldy, k, _p(G), ldg,
+                                     float(alpha), float(reg), _p(out), ldo, _p(status), _stream()),
+               'hsk_als_solve_f64')
     return out

@@ -918,6 +918,31 @@ int hsk_svd_score_rows(const int64_t* users, int64_t n_rows, int64_t n_users, co
                        const double* IF, int64_t ldi, int64_t n_items, int64_t k, const int64_t* excl_indptr,
                        const int32_t* excl_indices, double* out, int64_t ld, int32_t* status, hsk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ALS (algorithms/mf_algs.py:68-142): implicit-feedback alternating least squares, Cholesky-exact, all fp64.
+ * ------------------------------------------------------------------------------------------ */
+
+#define HSK_ALS_MAX_FACTORS 128
+
+/* One half-sweep: for every row r of the binary CSR (indptr int64 [n_rows + 1], indices int32, column ids in
+ * [0, n_cols)) against the other side's factors Y (n_cols x k, leading dimension ldy) and their Gram G = Y^T Y
+ * (k x k, ldg; hsk_svd_gram_f64 computes it):
+ *     A_r = G + reg I + (alpha - 1) sum_{i in row r} y_i y_i^T,   b_r = alpha sum_{i in row r} y_i,   X[r] = A_r^-1 b_r
+ * by Cholesky and two triangular solves; a row without entries gives X[r] = 0 exactly.  X is n_rows x k (ldx); the
+ * columns in [k, ldx) are never written.  One workgroup per row; `order` (NULL, or a permutation of [0, n_rows)) is
+ * the order in which the rows are issued (longest first keeps one popular item from being the grid's tail) and never
+ * changes a result (its entries are range-checked only: a row that a caller's `order` names twice is solved twice, and
+ * the row it leaves out is not written and raises no status bit): every sum has a fixed order, two calls give bitwise equal output.  Y and X are row-major,
+ * 16-byte aligned, with even leading dimensions >= k; G has ldg >= k of any parity, as hsk_svd_gram_f64 writes it.
+ * k outside [1, HSK_ALS_MAX_FACTORS], alpha or reg not finite
+ * and > 0: HSK_ERR_INVALID, nothing launched.  In *status: a column id outside [0, n_cols) (or an entry of `order`
+ * outside [0, n_rows)) sets HSK_STATUS_BAD_INDEX and is skipped; a pivot that is not positive and finite, or a
+ * solution that is not finite, sets HSK_STATUS_NOT_SPD and the row is written as zeros (with alpha, reg > 0 only
+ * non-finite input can do that). */
+int hsk_als_solve_f64(const int64_t* indptr, const int32_t* indices, int64_t n_rows, int64_t n_cols,
+                      const int32_t* order, const double* Y, int64_t ldy, int64_t k, const double* G, int64_t ldg,
+                      double alpha, double reg, double* X, int64_t ldx, int32_t* status, hsk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,7 @@ import logging
 import sys
 
 from hassaku_amd import experiment_helper as helper
-from hassaku_amd.algorithms.algorithms_utils import RUNNABLE_ALGORITHM_NAMES, AlgorithmsEnum
+from hassaku_amd.algorithms.algorithms_utils import OFFERED_ALGORITHM_NAMES, algorithm_by_name
 from hassaku_amd.conf.conf_parser import parse_conf_file
 from hassaku_amd.data.data_utils import DatasetsEnum
 
@@ -26,7 +26,7 @@ RUN_TYPES = {                      # -t value -> what it runs
 
 def _flags():
     """(names, argparse keywords) for every flag of the reference's CLI."""
-    yield ('-a', '--algorithm'), dict(choices=sorted(RUNNABLE_ALGORITHM_NAMES), metavar='ALG',
+    yield ('-a', '--algorithm'), dict(choices=sorted(OFFERED_ALGORITHM_NAMES), metavar='ALG',
                                       help='registry name of the model (%(choices)s)')
     yield ('-d', '--dataset'), dict(choices=sorted(m.name for m in DatasetsEnum), default='ml1m', metavar='DATASET',
                                     help='registry name of the dataset, default %(default)s')
@@ -50,7 +50,7 @@ def main(argv=None) -> int:
     if opts.measure_calibration:
         conf = parse_conf_file(conf)
         conf['measure_calibration'] = True
-    RUN_TYPES[opts.run_type](AlgorithmsEnum[opts.algorithm], DatasetsEnum[opts.dataset], conf)
+    RUN_TYPES[opts.run_type](algorithm_by_name(opts.algorithm), DatasetsEnum[opts.dataset], conf)
     return 0
 
 
