@@ -206,6 +206,10 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     'hsk_als_solve_f64': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                   c_int64, c_double, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
+    'hsk_slim_lds_candidates': (c_int64, []),
+    'hsk_slim_cd_ws_bytes': (c_int64, [c_int64]),
+    'hsk_slim_cd_f64': (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_double, c_double, c_double, c_int64,
+                                c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 

@@ -20,14 +20,19 @@ Trainer too, on a dataset that carries the item x tag matrix; `RUNNABLE_ALGORITH
 the other closed-form models).  It is not among the families `AlgorithmsEnum` looks through: `AlgorithmsEnum['als']`
 raises KeyError as it always has, and `RUNNABLE_ALGORITHM_NAMES` keeps its contents.  `algorithm_by_name(name)`
 resolves every slot, the new family included, and `OFFERED_ALGORITHM_NAMES` = `RUNNABLE_ALGORITHM_NAMES` + ('als',)
-is what run_experiment.py offers.
+lists them.
+
+`SparseLinearAlgorithmsEnum` holds `slim` (SLIM, one non-negative elastic net per item, fitted on the train CSR) in the
+same way: not among the families `AlgorithmsEnum` looks through (`AlgorithmsEnum['slim']` raises KeyError),
+resolved by `algorithm_by_name('slim')`, and `OFFERED_ALGORITHM_NAMES` keeps its contents.
+`AVAILABLE_ALGORITHM_NAMES` = `OFFERED_ALGORITHM_NAMES` + ('slim',) is what run_experiment.py offers.
 """
 from enum import Enum, EnumMeta
 
 from hassaku_amd.algorithms.ecf_alg import ECF
 from hassaku_amd.algorithms.graph_algs import P3alpha
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN
-from hassaku_amd.algorithms.linear_algs import EASE
+from hassaku_amd.algorithms.linear_algs import EASE, SLIM
 from hassaku_amd.algorithms.mf_algs import AlternatingLeastSquare, SVDAlgorithm
 from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
 from hassaku_amd.algorithms.proto_alg import ACF, IProtoMF, UIProtoMF, UProtoMF
@@ -61,6 +66,10 @@ class TagAlgorithmsEnum(Enum):
 
 class WeightedFactorAlgorithmsEnum(Enum):   # reached through algorithm_by_name(), not through AlgorithmsEnum
     als = AlternatingLeastSquare
+
+
+class SparseLinearAlgorithmsEnum(Enum):    # likewise
+    slim = SLIM
 
 
 _OTHER_FAMILIES = (SparseAlgorithmsEnum, LinearAlgorithmsEnum, GraphAlgorithmsEnum, FactorAlgorithmsEnum,
@@ -105,11 +114,16 @@ CLI_ALGORITHM_NAMES = REGISTERED_ALGORITHM_NAMES + tuple(m.name for m in FactorA
 EXPERIMENT_ALGORITHM_NAMES = CLI_ALGORITHM_NAMES + tuple(m.name for m in NeuralAlgorithmsEnum)
 RUNNABLE_ALGORITHM_NAMES = EXPERIMENT_ALGORITHM_NAMES + tuple(m.name for m in TagAlgorithmsEnum)
 OFFERED_ALGORITHM_NAMES = RUNNABLE_ALGORITHM_NAMES + tuple(m.name for m in WeightedFactorAlgorithmsEnum)
+AVAILABLE_ALGORITHM_NAMES = OFFERED_ALGORITHM_NAMES + tuple(m.name for m in SparseLinearAlgorithmsEnum)
 
 
 def algorithm_by_name(name: str):
-    """The slot called `name`: `AlgorithmsEnum[name]`, or the member of `WeightedFactorAlgorithmsEnum`."""
+    """The slot called `name`: `AlgorithmsEnum[name]`, or the member of `WeightedFactorAlgorithmsEnum` or of
+    `SparseLinearAlgorithmsEnum`."""
     try:
         return AlgorithmsEnum[name]
     except KeyError:
-        return WeightedFactorAlgorithmsEnum[name]
+        pass
+    if name in SparseLinearAlgorithmsEnum.__members__:
+        return SparseLinearAlgorithmsEnum[name]
+    return WeightedFactorAlgorithmsEnum[name]

@@ -1,6 +1,7 @@
-"""EASE on the HIP device (algorithms/linear_algs.py:131-176 of the reference; Steck, arXiv:1905.03375).
+"""EASE and SLIM on the HIP device (algorithms/linear_algs.py of the reference: EASE 131-176, Steck, arXiv:1905.03375;
+SLIM 14-128, described at its class below).
 
-fit(X), X the binary user x item train matrix:
+EASE.fit(X), X the binary user x item train matrix:
   * X^T is packed into the dense int8 operand of the neighbourhood models (hsk_knn_pack_i8) and the co-occurrence
     counts X^T X come block by block from the int8 matrix cores (hsk_knn_gram_i8, exact int32);
   * hsk_ease_gram_f64 turns a count block into rows of the fp64 G = X^T X + int(lam) I;
@@ -123,3 +124,137 @@ class EASE(FittedRecommenderAlgorithm):
     def build_from_conf(conf: dict, dataset):
         validate_ease_conf(conf)
         return EASE(conf['lam'])
+
+
+# ---------------------------------------------------------------------------------------------------------- SLIM
+def _number(conf: dict, key: str) -> float:
+    v = conf[key]
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f'{key} = {v!r} must be a number')
+    return float(v)
+
+
+def validate_slim_conf(conf: dict):
+    """The SLIM keys of a conf (linear_algs.py:128): `alpha` (finite and > 0), `l1_ratio` (a number in [0, 1]) and
+    `max_iter` (an integer >= 1), all required; anything else raises ValueError."""
+    for key in ('alpha', 'l1_ratio', 'max_iter'):
+        if key not in conf:
+            raise ValueError(f'SLIM conf needs {key}')
+    alpha, l1_ratio = _number(conf, 'alpha'), _number(conf, 'l1_ratio')
+    if not (math.isfinite(alpha) and alpha > 0):
+        raise ValueError(f"alpha = {conf['alpha']!r} must be finite and > 0")
+    if not 0 <= l1_ratio <= 1:       # false for nan
+        raise ValueError(f"l1_ratio = {conf['l1_ratio']!r} must be in [0, 1]")
+    max_iter = conf['max_iter']
+    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, (int, np.integer)):
+        raise ValueError(f'max_iter = {max_iter!r} must be an integer')
+    if max_iter < 1:
+        raise ValueError(f'max_iter = {max_iter!r} must be >= 1')
+
+
+class SLIM(FittedRecommenderAlgorithm):
+    """SLIM on the HIP device (algorithms/linear_algs.py:14-128 of the reference; Ning & Karypis, ICDM 2011).
+
+    fit(X): the exact G = X^T X as EASE builds it (int8 matrix cores, nothing added to the diagonal), then
+    hsk_slim_cd_f64 solves, per item j, the reference's ElasticNet(positive=True, fit_intercept=False, tol=1e-4) on X
+    with column j zeroed by cyclic coordinate descent on G alone (the reference draws coordinates at random: the
+    problem and the stop test are its, the iterates are the deterministic law of DESIGN.md section 5.10).  The model
+    keeps the dense fp64 item x item W (W[i, j] the weight of item i for target j) and the train CSR; score_rows() is
+    EASE's gather-sum, and the reference's dense users x items `pred_mtx = X @ W` is never built."""
+    GRAM_BLOCK_BYTES = EASE.GRAM_BLOCK_BYTES
+    WINDOW = EASE.WINDOW
+    TOL = 1e-4                 # the reference's ElasticNet(tol=...); an instance attribute `tol` overrides it
+
+    def __init__(self, alpha, l1_ratio, max_iter, device='cuda'):
+        super().__init__(device)
+        validate_slim_conf({'alpha': alpha, 'l1_ratio': l1_ratio, 'max_iter': max_iter})
+        self.alpha, self.l1_ratio, self.max_iter = float(alpha), float(l1_ratio), int(max_iter)
+        self.tol = self.TOL
+        self.name = 'SLIM'
+        self.W = None              # fp64 [n_items, n_items] on the device
+        self.n_iter_ = self.gap_ = None
+        logging.info('Built %s: alpha %s, l1_ratio %s, max_iter %d', self.name, alpha, l1_ratio, self.max_iter)
+
+    # ------------------------------------------------------------------ fit
+    _gram_block = EASE._gram_block
+
+    def penalties(self, n_users: int):
+        """(l1, l2) of the solver: sklearn's objective times n_users."""
+        return n_users * self.alpha * self.l1_ratio, n_users * self.alpha * (1 - self.l1_ratio)
+
+    def fit_bytes(self, n_users: int, n_items: int) -> int:
+        """Device bytes fit() allocates: G, Wt and W, the int8 operand of X^T, one count block and the workspace."""
+        rows_pad, k_pad = hip_ops.knn_pack_dims(n_items, n_users)
+        return (3 * 8 * n_items * n_items + rows_pad * k_pad + 4 * self._gram_block(n_items) * n_items +
+                hip_ops.slim_ws_bytes(n_items) + 12 * n_items)
+
+    def fit(self, matrix):
+        indptr, indices, n_users, n_items = csr_arrays(matrix)
+        dev = self.device
+        self._require_free(self.fit_bytes(n_users, n_items), f'{n_items} items')
+        self.W = self.pred_mtx = self.n_iter_ = self.gap_ = None     # a fit that raises leaves no model behind
+        x_ptr, x_idx, t_ptr, t_idx = self._upload(indptr, indices, transpose=(n_users, n_items))
+        M = hip_ops.knn_pack_i8(t_ptr, t_idx, n_items, n_users)
+        block = self._gram_block(n_items)
+        C = torch.empty((block, n_items), dtype=torch.int32, device=dev)
+        G = torch.empty((n_items, n_items), dtype=torch.float64, device=dev)
+        for r0 in range(0, n_items, block):
+            r1 = min(r0 + block, n_items)
+            hip_ops.knn_gram_i8(M, n_items, r0, r1, out=C)
+            hip_ops.ease_gram_f64(C, r1 - r0, r0, 0, G)
+        del M, C
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        l1, l2 = self.penalties(n_users)
+        Wt, n_iter, gap = hip_ops.slim_cd(G, l1, l2, self.tol, self.max_iter, status=status)
+        if int(status.item()) & hip_ops.STATUS_NOT_FINITE:
+            raise ValueError(f'{self.name}.fit: the solver met a non-finite value (HSK_STATUS_NOT_FINITE)')
+        del G
+        self.W = Wt.t().contiguous()
+        self.n_iter_, self.gap_ = n_iter, gap
+        self.train, self.n_users, self.n_items = (x_ptr, x_idx), n_users, n_items
+
+    def weights(self) -> np.ndarray:
+        """W as a numpy array [n_items, n_items]."""
+        return self.W.cpu().numpy()
+
+    # ------------------------------------------------------------------ scoring
+    def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
+        if self.pred_mtx is None and self.W is None:
+            raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
+        u = u_idxs.to(self.device, torch.int64).contiguous()
+        if self.pred_mtx is not None:
+            return self._dense_rows(u, excl)
+        return hip_ops.ease_score_rows(u, (*self.train, self.n_users), self.W, window=self.WINDOW, excl=excl, out=out,
+                                       status=self._status_word())
+
+    # ------------------------------------------------------------------ persistence
+    def save_model_to_path(self, path: str):
+        np.savez(os.path.join(path, 'model.npz'), alg=np.array('slim'), alpha=np.float64(self.alpha),
+                 l1_ratio=np.float64(self.l1_ratio), max_iter=np.int64(self.max_iter),
+                 n_users=np.int64(self.n_users), n_items=np.int64(self.n_items), W=self.weights(),
+                 train_indptr=self.train[0].cpu().numpy(), train_indices=self.train[1].cpu().numpy())
+        logging.info('Model Saved')
+
+    def load_model_from_path(self, path: str):
+        with np.load(os.path.join(path, 'model.npz')) as f:
+            if 'pred_mtx' in f:       # written by the reference (linear_algs.py:115-118): dense float64 predictions
+                self._load_pred_mtx(f)
+                self.W = None
+            else:
+                self._check_alg(f, 'slim')
+                n_users, n_items = int(f['n_users']), int(f['n_items'])
+                W = f['W']
+                if W.shape != (n_items, n_items) or W.dtype.kind != 'f':
+                    raise ValueError(f'W of model.npz is {W.dtype} {W.shape}, expected floats ({n_items}, {n_items})')
+                train = self._read_train(f, n_users, n_items)
+                self.n_users, self.n_items = n_users, n_items
+                self.W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(self.device)
+                self.train = self._upload(*train)
+                self.pred_mtx = None
+            self.n_iter_ = self.gap_ = None
+        logging.info('Model Loaded')
+
+    @staticmethod
+    def build_from_conf(conf: dict, dataset):
+        validate_slim_conf(conf)
+        return SLIM(conf['alpha'], conf['l1_ratio'], conf['max_iter'])

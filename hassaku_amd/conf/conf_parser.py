@@ -65,7 +65,7 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
     from hassaku_amd.algorithms.ecf_alg import ECF
     from hassaku_amd.algorithms.graph_algs import P3alpha, validate_p3alpha_conf
     from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
-    from hassaku_amd.algorithms.linear_algs import EASE, validate_ease_conf
+    from hassaku_amd.algorithms.linear_algs import EASE, SLIM, validate_ease_conf, validate_slim_conf
     from hassaku_amd.algorithms.mf_algs import (AlternatingLeastSquare, SVDAlgorithm, validate_als_conf,
                                                 validate_svd_conf)
     from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
@@ -77,6 +77,8 @@ def parse_conf(conf: dict, alg, dataset) -> dict:
         validate_knn_conf(conf)
     elif issubclass(alg.value, EASE):
         validate_ease_conf(conf)
+    elif issubclass(alg.value, SLIM):
+        validate_slim_conf(conf)
     elif issubclass(alg.value, P3alpha):
         validate_p3alpha_conf(conf)
     elif issubclass(alg.value, SVDAlgorithm):

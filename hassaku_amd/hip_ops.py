@@ -1398,3 +1398,52 @@ def als_solve(csr, Y: torch.Tensor, G: torch.Tensor, alpha: float, reg: float, o
                                      float(alpha), float(reg), _p(out), ldo, _p(status), _stream()),
                'hsk_als_solve_f64')
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# SLIM (hsk_slim.hip)
+# ---------------------------------------------------------------------------------------------------
+STATUS_NOT_FINITE = 16
+SLIM_LDS_CANDIDATES = 4096   # SLIM_LDS_CANDIDATES of csrc/hsk_slim.hip: columns with more candidates use the workspace
+
+
+def slim_ws_bytes(n: int) -> int:
+    return int(_lib.load().hsk_slim_cd_ws_bytes(int(n)))
+
+
+def slim_cd(G: torch.Tensor, l1: float, l2: float, tol: float, max_iter: int, j0: int = 0, j1: Optional[int] = None,
+            out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+            status: Optional[torch.Tensor] = None):
+    """(Wt fp64 [n, ld], n_iter int32 [n], gap fp64 [n]): cyclic coordinate descent of the SLIM columns [j0, j1) over
+    the symmetric fp64 Gram G [n, ld >= n]; row j of Wt holds the non-negative weights of target item j (Wt[j, j] = 0),
+    n_iter[j] the sweeps run and gap[j] the last duality gap.  Rows outside the range keep what `out` held (a new `out`
+    is zeros); n_iter and gap are 0 there.  l1 = n_users alpha l1_ratio, l2 = n_users alpha (1 - l1_ratio); tol = 0
+    runs max_iter sweeps unless a sweep changes nothing.  ws: a uint8 buffer of slim_ws_bytes(n).  status collects
+    HSK_STATUS_NOT_FINITE (16); without a caller's word a set bit raises ArithmeticError here."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    _chk(G, torch.float64, 'G')
+    if G.dim() != 2 or G.shape[1] < G.shape[0]:
+        raise ValueError(f'G has shape {tuple(G.shape)}, expected [n, ld >= n]')
+    n, ld = G.shape
+    j1 = n if j1 is None else j1
+    if out is None:
+        out = torch.zeros((n, n), dtype=torch.float64, device=G.device)
+    _chk(out, torch.float64, 'out')
+    if out.dim() != 2 or out.shape[0] != n or out.shape[1] < n:
+        raise ValueError(f'out has shape {tuple(out.shape)}, expected [{n}, ld >= {n}]')
+    need = slim_ws_bytes(n)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=G.device)
+    _chk(ws, torch.uint8, 'ws')
+    own = status is None
+    status = _status_word(status, G.device)
+    _chk(status, torch.int32, 'status', (1,))
+    n_iter = torch.zeros(n, dtype=torch.int32, device=G.device)
+    gap = torch.zeros(n, dtype=torch.float64, device=G.device)
+    _lib.check(lib.hsk_slim_cd_f64(_p(G), n, ld, int(j0), int(j1), float(l1), float(l2), float(tol), int(max_iter),
+                                   _p(out), out.shape[1], _p(n_iter), _p(gap), _p(ws), ws.numel(), _p(status),
+                                   _stream()), 'hsk_slim_cd_f64')
+    if own and int(status.item()) & STATUS_NOT_FINITE:
+        raise ArithmeticError('slim_cd: a non-finite entry of G, weight or gap (HSK_STATUS_NOT_FINITE)')
+    return out, n_iter, gap

@@ -943,6 +943,37 @@ int hsk_als_solve_f64(const int64_t* indptr, const int32_t* indices, int64_t n_r
                       const int32_t* order, const double* Y, int64_t ldy, int64_t k, const double* G, int64_t ldg,
                       double alpha, double reg, double* X, int64_t ldx, int32_t* status, hsk_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * SLIM (algorithms/linear_algs.py:14-128): per item one non-negative elastic net over the shared Gram, all fp64.
+ * ------------------------------------------------------------------------------------------ */
+
+enum { HSK_STATUS_NOT_FINITE = 16 }; /* hsk_slim_cd_f64 met a non-finite entry of G, weight or gap */
+
+/* the largest candidate set whose g, d, q, w a workgroup of hsk_slim_cd_f64 keeps in LDS (longer columns use the
+ * workspace; the results are the same bits) */
+int64_t hsk_slim_lds_candidates(void);
+
+/* bytes of the workspace of hsk_slim_cd_f64 (0 for an n it refuses) */
+int64_t hsk_slim_cd_ws_bytes(int64_t n);
+
+/* Cyclic coordinate descent for the columns j in [j0, j1) of SLIM over the symmetric fp64 G = X^T X (n x n, leading
+ * dimension ld; row i is read as column i).  With d_i = G_ii, g_i = G_ij and q_i = sum_{k != j} G_ik w_k, from w = 0 one
+ * sweep visits i = 0 .. n - 1 ascending, skipping i = j and d_i = 0:
+ *     t = g_i - (q_i - d_i w_i) - l1;  new = t > 0 ? t / (d_i + l2) : 0;  if new != w_i: q_k += (new - w_i) G_ik, w_i = new
+ * every operation rounded on its own (no fma), so Wt and n_iter are the bits of any other evaluation of this law.
+ * After sweep `it`, if wmax == 0, dmax <= tol wmax or it == max_iter (dmax = max |new - old|, wmax = max |new| of the
+ * sweep), sklearn's duality gap is evaluated (sums in a fixed order: two calls give equal bits) and the column stops
+ * when gap <= tol G_jj; it also stops at it == max_iter, and with tol == 0 the gap decides nothing and a sweep with
+ * dmax == 0 stops.  Only the candidates {i : g_i > l1, d_i > 0, i != j} are visited: with G >= 0 no other coordinate
+ * leaves 0.  Output: Wt[j, i] = w_i for i < n (n x n, ldw; rows outside the range and columns in [n, ldw) are not
+ * written), n_iter[j] the sweeps run, gap[j] the last gap evaluated.  workspace: device memory, 256-byte aligned,
+ * workspace_bytes >= hsk_slim_cd_ws_bytes(n).  HSK_ERR_INVALID, nothing launched: a null pointer, n outside
+ * [1, 2^31 - 1), ld or ldw < n, a range not inside [0, n) or empty, max_iter < 1, l1, l2 or tol negative or not finite.
+ * A non-finite entry of G met on the way, weight or gap sets HSK_STATUS_NOT_FINITE in *status. */
+int hsk_slim_cd_f64(const double* G, int64_t n, int64_t ld, int64_t j0, int64_t j1, double l1, double l2, double tol,
+                    int64_t max_iter, double* Wt, int64_t ldw, int32_t* n_iter, double* gap, void* workspace,
+                    int64_t workspace_bytes, int32_t* status, hsk_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ import logging
 import sys
 
 from hassaku_amd import experiment_helper as helper
-from hassaku_amd.algorithms.algorithms_utils import OFFERED_ALGORITHM_NAMES, algorithm_by_name
+from hassaku_amd.algorithms.algorithms_utils import (AVAILABLE_ALGORITHM_NAMES, OFFERED_ALGORITHM_NAMES,
+                                                        algorithm_by_name)
 from hassaku_amd.conf.conf_parser import parse_conf_file
 from hassaku_amd.data.data_utils import DatasetsEnum
 
@@ -26,8 +27,10 @@ RUN_TYPES = {                      # -t value -> what it runs
 
 def _flags():
     """(names, argparse keywords) for every flag of the reference's CLI."""
-    yield ('-a', '--algorithm'), dict(choices=sorted(OFFERED_ALGORITHM_NAMES), metavar='ALG',
-                                      help='registry name of the model (%(choices)s)')
+    later = ', '.join(n for n in AVAILABLE_ALGORITHM_NAMES if n not in OFFERED_ALGORITHM_NAMES)
+    yield ('-a', '--algorithm'), dict(choices=sorted(AVAILABLE_ALGORITHM_NAMES), metavar='ALG',
+                                      help=f"registry name of the model ({', '.join(sorted(OFFERED_ALGORITHM_NAMES))})"
+                                           f' or {later}')
     yield ('-d', '--dataset'), dict(choices=sorted(m.name for m in DatasetsEnum), default='ml1m', metavar='DATASET',
                                     help='registry name of the dataset, default %(default)s')
     yield ('-c', '--conf_path'), dict(metavar='FILE', help='YAML (or JSON) file with the experiment configuration')
