@@ -104,6 +104,7 @@ def _tag_factors(tag_matrix, n_items: int):
 
 class ECF(_HipTables):
     DENSE_KEYS = ('tag_matrix', 'interaction_matrix')   # of a reference-written model.pth, if it was handed float32
+    validate_conf = staticmethod(validate_ecf_conf)   # its own keys; the SGD defaults apply as for any trained model
 
     def __init__(self, n_users: int, n_items: int, tag_matrix, interaction_matrix, embedding_dim: int = 100,
                  n_clusters: int = 64, top_n: int = 20, top_m: int = 20, temp_masking: float = 2.,

@@ -14,44 +14,39 @@ scales by w_u and raises to alpha.  Every term is positi
 bounded by the number of three-step paths, whatever order either side adds in.
 """
 import logging
-import math
-import os
 
 import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays
-
-
-def _alpha(alpha) -> float:
-    """alpha as a float, refusing what has no such value or is not positive (the reference asserts alpha >= 0, but its
-    `.power(0)` raises inside scipy)."""
-    if isinstance(alpha, (bool, np.bool_)) or not isinstance(alpha, (int, float, np.integer, np.floating)):
-        raise ValueError(f'alpha = {alpha!r} must be a number')
-    if not math.isfinite(alpha) or not alpha > 0:
-        raise ValueError(f'alpha = {alpha!r} must be a finite number > 0')
-    return float(alpha)
+from hassaku_amd.algorithms.base_classes import ItemWeightAlgorithm, csr_arrays
+from hassaku_amd.conf import checks
 
 
 def validate_p3alpha_conf(conf: dict):
-    """The P3alpha key of a conf (graph_algs.py:86-88): `alpha`, required as the reference's build_from_conf does."""
-    if 'alpha' not in conf:
-        raise ValueError('P3alpha conf needs alpha')
-    _alpha(conf['alpha'])
+    """The P3alpha key of a conf (graph_algs.py:86-88): `alpha`, required as the reference's build_from_conf does;
+    finite and > 0 (the reference asserts alpha >= 0, but its `.power(0)` raises inside scipy)."""
+    checks.require(conf, 'P3alpha', 'alpha')
+    checks.positive('alpha', conf['alpha'])
 
 
-class P3alpha(FittedRecommenderAlgorithm):
+class P3alpha(ItemWeightAlgorithm):
+    ALG, WEIGHTS = 'p3alpha', 'W'
     GRAM_BLOCK_ROWS = 4096       # rows of W per launch of the Gram kernel (a multiple of 128)
-    WINDOW = 1024                # item window of one scoring workgroup
+    validate_conf = staticmethod(validate_p3alpha_conf)
 
     def __init__(self, alpha=1.9, device='cuda'):
         super().__init__(device)
-        self.alpha = _alpha(alpha)
+        self.alpha = checks.positive('alpha', alpha)
         self.name = 'P3alpha'
-        self.W = None              # fp64 [n_items, n_items] on the device
-        self.inv_deg_u = None      # fp64 [n_users]: 1 / user degree, 0 for users without items
         logging.info('Built %s: alpha %s', self.name, self.alpha)
+
+    def _forget(self):
+        super()._forget()
+        self.inv_deg_u = None      # fp64 [n_users]: 1 / user degree, 0 for users without items
+
+    def hyper(self) -> dict:
+        return dict(alpha=np.float64(self.alpha))
 
     # ------------------------------------------------------------------ fit
     def fit_bytes(self, n_users: int, n_items: int) -> int:
@@ -59,43 +54,32 @@ class P3alpha(FittedRecommenderAlgorithm):
         rows_pad, k_pad = hip_ops.knn_pack_dims(n_items, n_users)
         return 8 * n_items * n_items + rows_pad * k_pad + 8 * (k_pad + n_items)
 
-    def fit(self, matrix):
-        indptr, indices, n_users, n_items = csr_arrays(matrix)
-        dev = self.device
-        self._require_free(self.fit_bytes(n_users, n_items), f'{n_items} items')
-        self.W = self.pred_mtx = self.inv_deg_u = None     # a fit that raises leaves no model behind
-        x_ptr, x_idx, t_ptr, t_idx = self._upload(indptr, indices, transpose=(n_users, n_items))
-        M = hip_ops.knn_pack_i8(t_ptr, t_idx, n_items, n_users)
-        w_u = hip_ops.p3_inv_degrees(x_ptr, M.shape[1])     # zero on the padding of k
-        w_i = hip_ops.p3_inv_degrees(t_ptr)
-        W = torch.empty((n_items, n_items), dtype=torch.float64, device=dev)
+    @staticmethod
+    def _degrees(x_ptr, t_ptr, k_pad: int):
+        """(w_u padded with zeros to the operand's k, w_i)."""
+        return hip_ops.p3_inv_degrees(x_ptr, k_pad), hip_ops.p3_inv_degrees(t_ptr)
+
+    def _weighted_gram(self, M, n_items: int, w_u, w_i):
+        W = torch.empty((n_items, n_items), dtype=torch.float64, device=self.device)
         for r0 in range(0, n_items, self.GRAM_BLOCK_ROWS):
             hip_ops.p3_gram_f64(M, n_items, w_u, r0, min(r0 + self.GRAM_BLOCK_ROWS, n_items), W, row_scale=w_i)
-        del M
-        self.W, self.inv_deg_u = W, w_u[:n_users].contiguous()
-        self.train, self.n_users, self.n_items = (x_ptr, x_idx), n_users, n_items
+        return W
 
-    def weights(self) -> np.ndarray:
-        """W as a numpy array [n_items, n_items]."""
-        return self.W.cpu().numpy()
+    def fit(self, matrix):
+        indptr, indices, n_users, n_items = csr_arrays(matrix)
+        self._require_free(self.fit_bytes(n_users, n_items), f'{n_items} items')
+        self._forget()                    # a fit that raises leaves no model behind
+        train, t_ptr, M = self._pack(indptr, indices, n_users, n_items)
+        w_u, w_i = self._degrees(train[0], t_ptr, M.shape[1])
+        self.W = self._weighted_gram(M, n_items, w_u, w_i)
+        self.inv_deg_u = w_u[:n_users].contiguous()
+        self.train, self.n_users, self.n_items = train, n_users, n_items
 
     # ------------------------------------------------------------------ scoring
-    def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
-        u = u_idxs.to(self.device, torch.int64).contiguous()
-        if self.pred_mtx is not None:
-            return self._dense_rows(u, excl)
-        if self.W is None:
-            raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
-        return hip_ops.p3_score_rows(u, (*self.train, self.n_users), self.W, self.inv_deg_u, self.alpha,
-                                     window=self.WINDOW, excl=excl, out=out, status=self._status_word())
+    def _score(self, u, W, **kw):
+        return hip_ops.p3_score_rows(u, (*self.train, self.n_users), W, self.inv_deg_u, self.alpha, **kw)
 
     # ------------------------------------------------------------------ persistence
-    def save_model_to_path(self, path: str):
-        np.savez(os.path.join(path, 'model.npz'), alg=np.array('p3alpha'), alpha=np.float64(self.alpha),
-                 n_users=np.int64(self.n_users), n_items=np.int64(self.n_items), W=self.weights(),
-                 train_indptr=self.train[0].cpu().numpy(), train_indices=self.train[1].cpu().numpy())
-        logging.info('Model Saved')
-
     @staticmethod
     def _read_pred_mtx(f) -> np.ndarray:
         try:
@@ -113,29 +97,12 @@ class P3alpha(FittedRecommenderAlgorithm):
             raise ValueError('pred_mtx of model.npz must be a dense 2-D float array')
         return pred
 
-    def load_model_from_path(self, path: str):
-        dev = self.device
-        with np.load(os.path.join(path, 'model.npz')) as f:       # never with allow_pickle
-            if 'pred_mtx' in f:
-                self._load_pred_mtx(f)
-                self.W = self.inv_deg_u = None
-            else:
-                self._check_alg(f, 'p3alpha')
-                n_users, n_items = int(f['n_users']), int(f['n_items'])
-                alpha = _alpha(float(f['alpha']))
-                W = f['W']
-                if W.shape != (n_items, n_items):
-                    raise ValueError(f'W of model.npz has shape {W.shape}, expected ({n_items}, {n_items})')
-                t_ptr, t_idx = self._read_train(f, n_users, n_items)
-                deg = np.diff(t_ptr)
-                w_u = np.zeros(n_users, np.float64)
-                w_u[deg > 0] = 1.0 / deg[deg > 0]        # one IEEE division each, as hsk_p3_inv_degrees
-                self.n_users, self.n_items, self.alpha = n_users, n_items, alpha
-                self.W = torch.from_numpy(np.ascontiguousarray(W, np.float64)).to(dev)
-                self.inv_deg_u = torch.from_numpy(w_u).to(dev)
-                self.train = self._upload(t_ptr, t_idx)
-                self.pred_mtx = None
-        logging.info('Model Loaded')
+    def _load_own(self, f, t_ptr):
+        self.alpha = checks.positive('alpha', float(f['alpha']))
+        deg = np.diff(t_ptr)
+        w_u = np.zeros(len(deg), np.float64)
+        w_u[deg > 0] = 1.0 / deg[deg > 0]        # one IEEE division each, as hsk_p3_inv_degrees
+        self.inv_deg_u = torch.from_numpy(w_u).to(self.device)
 
     @staticmethod
     def build_from_conf(conf: dict, dataset):

@@ -18,6 +18,7 @@ import torch
 
 from hassaku_amd import hip_ops
 from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays, csr_transpose
+from hassaku_amd.conf import checks
 
 
 class SimilarityFunctionEnum(Enum):
@@ -46,24 +47,19 @@ def validate_knn_conf(conf: dict):
     for key in _needs(SimilarityFunctionEnum[name]):
         if params.get(key) is None:
             raise ValueError(f'sim_func_name {name} needs sim_func_params.{key}')
-    if 'k' not in conf:
-        raise ValueError('KNN conf needs k')
-    k = conf['k']
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= hip_ops.KNN_MAX_K:
-        raise ValueError(f'k = {k!r} must be an integer in [1, {hip_ops.KNN_MAX_K}]')
-    shrinkage = conf.get('shrinkage', 0.)
-    if isinstance(shrinkage, bool) or not isinstance(shrinkage, (int, float, np.number)) or not shrinkage >= 0:
-        raise ValueError(f'shrinkage = {shrinkage!r} must be a number >= 0')
+    checks.require(conf, 'KNN', 'k')
+    checks.integer('k', conf['k'], 1, hip_ops.KNN_MAX_K)
+    if not checks.number('shrinkage', conf.get('shrinkage', 0.)) >= 0:
+        raise ValueError(f"shrinkage = {conf['shrinkage']!r} must be a number >= 0")
 
 
 _transpose = csr_transpose     # the name this module had it under; tests/test_ease.py and test_p3alpha.py import it
 
-
 class KNNAlgorithm(FittedRecommenderAlgorithm):
     """Common part of UserKNN / ItemKNN (knn_algs.py:13-72)."""
-    GRAM_BLOCK_BYTES = 1 << 30   # int32 counts of one row block
     WINDOW = 4096                # item window of one scoring wave (fp64 accumulators in LDS)
     ITEM_BASED = False
+    validate_conf = staticmethod(validate_knn_conf)
 
     def __init__(self, sim_func_enum: SimilarityFunctionEnum = SimilarityFunctionEnum.cosine, k: int = 100,
                  shrinkage: float = .0, device='cuda', **kwargs):
@@ -79,13 +75,17 @@ class KNNAlgorithm(FittedRecommenderAlgorithm):
         self.alpha, self.beta = kwargs.get('alpha'), kwargs.get('beta')
         self.k, self.shrinkage = int(k), float(shrinkage)
         self.name = 'KNNAlgorithm'
-        self.neigh = None          # (indptr int64, indices int32, vals fp64) of S, stored order
-        self._b_t = None           # S^T (ItemKNN scoring)
         logging.info('Built %s: sim_func %s, k %d, shrinkage %s', self.name, sim_func_enum.name, self.k, self.shrinkage)
 
+    def _forget(self):
+        super()._forget()
+        self.neigh = None          # (indptr int64, indices int32, vals fp64) of S, stored order
+        self._b_t = None           # S^T (ItemKNN scoring)
+
     # ------------------------------------------------------------------ fit
-    def fit(self, matrix):
-        indptr, indices, n_users, n_items = csr_arrays(matrix)
+    def _pack(self, indptr, indices, n_users, n_items):
+        """Uploads X as the train CSR and packs the entity matrix (X^T for ItemKNN, X for UserKNN): (the dense int8
+        operand, its number of rows, the degree vectors hsk_knn_select reads: deg, sqrt, deg^alpha, deg^(1-alpha))."""
         dev = self.device
         up = self._upload(indptr, indices, transpose=(n_users, n_items) if self.ITEM_BASED else None)
         self.train, self.n_users, self.n_items = up[:2], n_users, n_items
@@ -98,20 +98,22 @@ class KNNAlgorithm(FittedRecommenderAlgorithm):
         if sim == SimilarityFunctionEnum.asymmetric_cosine:
             pa, p1a = put(np.power(deg, self.alpha)), put(np.power(deg, 1 - self.alpha))
         deg_d = torch.from_numpy(deg).to(dev)
-        M = hip_ops.knn_pack_i8(e_ptr, e_idx, n_ent, n_feat)
-        block = max(128, (self.GRAM_BLOCK_BYTES // (4 * n_ent)) // 128 * 128)
-        block = min(block, -(-n_ent // 128) * 128)
-        C = torch.empty((block, n_ent), dtype=torch.int32, device=dev)
+        return hip_ops.knn_pack_i8(e_ptr, e_idx, n_ent, n_feat), n_ent, (deg_d, sq, pa, p1a)
+
+    def _select(self, C, r0: int, r1: int, degrees):
+        """(idx, val, len) of the k nearest neighbours of rows [r0, r1) from their count block."""
+        return hip_ops.knn_select(C, r1 - r0, r0, *degrees, self.sim_func_enum.name, self.alpha, self.beta,
+                                  self.shrinkage, min(self.k, hip_ops.KNN_MAX_K))
+
+    def fit(self, matrix):
+        dev = self.device
+        M, n_ent, degrees = self._pack(*csr_arrays(matrix))
         k = min(self.k, hip_ops.KNN_MAX_K)
         idx = torch.empty((n_ent, k), dtype=torch.int32, device=dev)
         val = torch.empty((n_ent, k), dtype=torch.float64, device=dev)
         ln = torch.empty(n_ent, dtype=torch.int32, device=dev)
-        for r0 in range(0, n_ent, block):
-            r1 = min(r0 + block, n_ent)
-            hip_ops.knn_gram_i8(M, n_ent, r0, r1, out=C)
-            bi, bv, bl = hip_ops.knn_select(C, r1 - r0, r0, deg_d, sq, pa, p1a, sim.name, self.alpha, self.beta,
-                                            self.shrinkage, k)
-            idx[r0:r1], val[r0:r1], ln[r0:r1] = bi, bv, bl
+        for r0, r1, C in self._count_blocks(M, n_ent):
+            idx[r0:r1], val[r0:r1], ln[r0:r1] = self._select(C, r0, r1, degrees)
         del M, C
         keep = torch.arange(k, device=dev)[None, :] < ln[:, None]
         s_ptr = torch.zeros(n_ent + 1, dtype=torch.int64, device=dev)
@@ -154,18 +156,16 @@ class KNNAlgorithm(FittedRecommenderAlgorithm):
 
     def load_model_from_path(self, path: str):
         dev = self.device
+        self._forget()                # a load that raises leaves no model behind
         with np.load(os.path.join(path, 'model.npz')) as f:
             if 'pred_mtx' in f:       # written by the reference (knn_algs.py:46-56): dense float64 predictions
                 self._load_pred_mtx(f)
-                self.neigh = None
             else:
                 self._check_alg(f, 'iknn' if self.ITEM_BASED else 'uknn')
                 self.n_users, self.n_items = int(f['n_users']), int(f['n_items'])
                 self.neigh = (torch.from_numpy(f['neigh_indptr']).to(dev), torch.from_numpy(f['neigh_indices']).to(dev),
                               torch.from_numpy(f['neigh_data']).to(dev))
                 self.train = self._upload(*self._read_train(f, self.n_users, self.n_items, validate=False))
-                self.pred_mtx = None
-            self._b_t = None
         logging.info('Model Loaded')
 
     @staticmethod

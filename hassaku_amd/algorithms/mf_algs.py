@@ -19,45 +19,33 @@ The reference's dense users x items product is never built: score_rows() multipl
 matrix cores.  svds' ascending column order and its signs are not reproduced; the product of the factors is what the
 two share."""
 import logging
-import os
 
 import numpy as np
 import torch
 
 from hassaku_amd import hip_ops
-from hassaku_amd.algorithms.base_classes import FittedRecommenderAlgorithm, csr_arrays
-
-
-def _n_factors(n_factors) -> int:
-    """n_factors as an int, refusing bools, non-integers and values below 1."""
-    if isinstance(n_factors, (bool, np.bool_)) or not isinstance(n_factors, (int, np.integer)):
-        raise ValueError(f'n_factors = {n_factors!r} must be an integer')
-    if n_factors < 1:
-        raise ValueError(f'n_factors = {n_factors!r} must be >= 1')
-    return int(n_factors)
+from hassaku_amd.algorithms.base_classes import FactorAlgorithm, csr_arrays
+from hassaku_amd.conf import checks
 
 
 def validate_svd_conf(conf: dict):
     """The SVD key of a conf (mf_algs.py:65): `n_factors`, required as the reference's build_from_conf does."""
-    if 'n_factors' not in conf:
-        raise ValueError('SVDAlgorithm conf needs n_factors')
-    _n_factors(conf['n_factors'])
+    checks.require(conf, 'SVDAlgorithm', 'n_factors')
+    checks.integer('n_factors', conf['n_factors'], 1)
 
 
-class SVDAlgorithm(FittedRecommenderAlgorithm):
+class SVDAlgorithm(FactorAlgorithm):
+    ALG, WIDTH, MAX_K = 'svd', 'n_factors', hip_ops.SVD_MAX_BLOCK
     OVERSAMPLE = 32              # columns of the block beyond n_factors (before rounding up to 16)
     TOL = 1e-11                  # residual of the n_factors leading Ritz pairs, relative to theta_1
     MAX_ITER = 1000
     SEED = 0                     # of the host-made start block
+    validate_conf = staticmethod(validate_svd_conf)
 
     def __init__(self, n_factors=100, device='cuda'):
-        super().__init__(device)          # pred_mtx and train stay None: the factors are all a model or a file holds
-        self.n_factors = _n_factors(n_factors)
+        super().__init__(device)
+        self.n_factors = checks.integer('n_factors', n_factors, 1)
         self.name = 'SVDAlgorithm'
-        self.users_factors = None     # fp64 [n_users, k] on the device (= U S); a view of an even-stride buffer
-        self.items_factors = None     # fp64 [n_items, k]
-        self.singular_values = None   # numpy float64 [k], descending (None for a model loaded from the reference)
-        self.n_iter_ = self.residual_ = None
         logging.info('Built %s: n_factors %d', self.name, self.n_factors)
 
     # ------------------------------------------------------------------ fit
@@ -76,8 +64,12 @@ class SVDAlgorithm(FittedRecommenderAlgorithm):
         return max(hip_ops.svd_gram_ws_bytes(n, w) for n in (n_users, n_items) for w in range(1, b + 1))
 
     def _forget(self):
-        self.users_factors = self.items_factors = self.singular_values = None
+        super()._forget()             # users_factors = U S
+        self.singular_values = None   # numpy float64 [k], descending (None for a model loaded from the reference)
         self.n_iter_ = self.residual_ = None
+
+    def hyper(self) -> dict:
+        return dict(n_factors=np.int64(self.n_factors), singular_values=self.singular_values)
 
     def _orth(self, Y, scratch, out, ws):
         """orth(Y) into the leading columns of `out`, the normalised block in `scratch` (both [n, >= width])."""
@@ -144,43 +136,13 @@ class SVDAlgorithm(FittedRecommenderAlgorithm):
         self.n_users, self.n_items = n_users, n_items
         self.n_iter_, self.residual_ = it, residual
 
-    # ------------------------------------------------------------------ scoring
-    def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
-        if self.items_factors is None:
-            raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
-        u = u_idxs.to(self.device, torch.int64).contiguous()
-        return hip_ops.svd_score_rows(u, self.users_factors, self.items_factors, excl=excl, out=out,
-                                      status=self._status_word())
-
     # ------------------------------------------------------------------ persistence
-    def save_model_to_path(self, path: str):
-        """The reference's two keys (mf_algs.py:51-54) plus alg, n_factors and singular_values, which its loader
-        ignores."""
-        np.savez(os.path.join(path, 'model.npz'), users_factors=self.users_factors.cpu().numpy(),
-                 items_factors=self.items_factors.cpu().numpy(), alg=np.array('svd'),
-                 n_factors=np.int64(self.n_factors), singular_values=self.singular_values)
-        logging.info('Model Saved')
-
-    def load_model_from_path(self, path: str):
-        """Reads a file written here or by the reference (no `alg` key; float32 if its svds ran on the float32 cast of
-        an integer matrix -- any float dtype is taken and held as float64)."""
-        with np.load(os.path.join(path, 'model.npz')) as f:       # never with allow_pickle
-            uf, vf, k = _read_factors(f, 'svd', self.name, hip_ops.SVD_MAX_BLOCK)
-            if 'n_factors' in f and int(f['n_factors']) != k:
-                raise ValueError(f"n_factors = {int(f['n_factors'])} of model.npz, but the factors have {k} columns")
-            sv = None
-            if 'singular_values' in f:
-                sv = np.asarray(f['singular_values'], np.float64)
-                if sv.shape != (k,):
-                    raise ValueError(f'singular_values of model.npz has shape {sv.shape}, expected ({k},)')
-        self._forget()
-        self.n_factors, self.singular_values = k, sv
-        self.n_users, self.n_items = uf.shape[0], vf.shape[0]
-        self.users_factors, self.items_factors = self._padded(uf), self._padded(vf)
-        logging.info('Model Loaded')
-
-    def _padded(self, a: np.ndarray) -> torch.Tensor:
-        return _padded(a, self.device)
+    def _load_own(self, f, k: int):
+        if 'singular_values' in f:
+            sv = np.asarray(f['singular_values'], np.float64)
+            if sv.shape != (k,):
+                raise ValueError(f'singular_values of model.npz has shape {sv.shape}, expected ({k},)')
+            self.singular_values = sv
 
     @staticmethod
     def build_from_conf(conf: dict, dataset):
@@ -189,73 +151,22 @@ class SVDAlgorithm(FittedRecommenderAlgorithm):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# what the two factor models share: the two keys of the reference's model.npz and the padded device layout
-# ---------------------------------------------------------------------------------------------------------------
-def _read_factors(f, alg: str, name: str, max_k: int):
-    """(users_factors, items_factors, k) of an open model.npz written here (`alg` must match) or by the reference (no
-    `alg` key; any float dtype), validated: two 2-D float arrays that share a number of factors in [1, max_k]."""
-    if 'alg' in f and str(f['alg']) != alg:
-        raise ValueError(f"model.npz holds a {str(f['alg'])} model, not {name}")
-    for key in ('users_factors', 'items_factors'):
-        if key not in f:
-            raise ValueError(f'model.npz has no {key}')
-    try:
-        uf, vf = f['users_factors'], f['items_factors']
-    except ValueError as e:
-        raise ValueError('the factors of model.npz are object arrays; they are not unpickled') from e
-    for key, a in (('users_factors', uf), ('items_factors', vf)):
-        if a.ndim != 2 or not np.issubdtype(a.dtype, np.floating):
-            raise ValueError(f'{key} of model.npz must be a 2-D float array, got {a.dtype} {a.shape}')
-    k = uf.shape[1]
-    if vf.shape[1] != k or not 1 <= k <= max_k or uf.shape[0] < 1 or vf.shape[0] < 1:
-        raise ValueError(f'users_factors {uf.shape} and items_factors {vf.shape} of model.npz do not share a '
-                         f'number of factors in [1, {max_k}]')
-    return uf, vf, k
-
-
-def _padded(a: np.ndarray, device) -> torch.Tensor:
-    """[n, k] float64 on the device as a view of an even-stride buffer (16-byte aligned rows for any k)."""
-    buf = np.zeros((a.shape[0], hip_ops.svd_ld(a.shape[1])), np.float64)
-    buf[:, :a.shape[1]] = a
-    return torch.from_numpy(buf).to(device)[:, :a.shape[1]]
-
-
-# ---------------------------------------------------------------------------------------------------------------
 # ALS
 # ---------------------------------------------------------------------------------------------------------------
-def _als_int(conf_key: str, v, lo: int, hi=None) -> int:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        raise ValueError(f'{conf_key} = {v!r} must be an integer')
-    if v < lo or (hi is not None and v > hi):
-        raise ValueError(f'{conf_key} = {v!r} must be in [{lo}, {hi}]' if hi is not None else
-                         f'{conf_key} = {v!r} must be >= {lo}')
-    return int(v)
-
-
-def _als_positive(conf_key: str, v) -> float:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f'{conf_key} = {v!r} must be a number')
-    if not (np.isfinite(v) and v > 0):
-        raise ValueError(f'{conf_key} = {v!r} must be finite and > 0')
-    return float(v)
-
-
 def validate_als_conf(conf: dict):
     """The ALS keys of a conf (mf_algs.py:139-142): `alpha`, `factors`, `regularization`, `n_iterations`, required as
     the reference's build_from_conf indexes them; `use_gpu` is optional, a bool, and changes nothing.
     regularization = 0, which the reference takes (and may then invert a singular matrix), is refused."""
-    for key in ('alpha', 'factors', 'regularization', 'n_iterations'):
-        if key not in conf:
-            raise ValueError(f'AlternatingLeastSquare conf needs {key}')
-    _als_positive('alpha', conf['alpha'])
-    _als_int('factors', conf['factors'], 1, hip_ops.ALS_MAX_FACTORS)
-    _als_positive('regularization', conf['regularization'])
-    _als_int('n_iterations', conf['n_iterations'], 1)
+    checks.require(conf, 'AlternatingLeastSquare', 'alpha', 'factors', 'regularization', 'n_iterations')
+    checks.positive('alpha', conf['alpha'])
+    checks.integer('factors', conf['factors'], 1, hip_ops.ALS_MAX_FACTORS)
+    checks.positive('regularization', conf['regularization'])
+    checks.integer('n_iterations', conf['n_iterations'], 1)
     if 'use_gpu' in conf and not isinstance(conf['use_gpu'], (bool, np.bool_)):
         raise ValueError(f"use_gpu = {conf['use_gpu']!r} must be a bool")
 
 
-class AlternatingLeastSquare(FittedRecommenderAlgorithm):
+class AlternatingLeastSquare(FactorAlgorithm):
     """Implicit-feedback ALS (Hu, Koren, Volinsky; mf_algs.py:68-142 of the reference, which calls the `implicit`
     package) on the HIP device, DESIGN.md section 5.9.  X is the binary train matrix, a stored entry has confidence
     alpha and preference 1, every other entry confidence 1 and preference 0.  One half-sweep solves every row r of a
@@ -267,20 +178,18 @@ class AlternatingLeastSquare(FittedRecommenderAlgorithm):
     new users.  The start is RandomState(SEED).random_sample((n_users, k)) * 0.01, then the same call for the items,
     made on the host: `implicit`'s CPU law, not its random stream; its default three conjugate-gradient steps are not
     reproduced (this is its use_cg=False)."""
+    ALG, WIDTH, MAX_K = 'als', 'factors', hip_ops.ALS_MAX_FACTORS
     SEED = 0
+    validate_conf = staticmethod(validate_als_conf)
 
     def __init__(self, alpha, factors, regularization, n_iterations, use_gpu=True, device='cuda'):
         super().__init__(device)
-        self.alpha = _als_positive('alpha', alpha)
-        self.factors = _als_int('factors', factors, 1, hip_ops.ALS_MAX_FACTORS)
-        self.regularization = _als_positive('regularization', regularization)
-        self.n_iterations = _als_int('n_iterations', n_iterations, 1)
-        if not isinstance(use_gpu, (bool, np.bool_)):
-            raise ValueError(f'use_gpu = {use_gpu!r} must be a bool')
+        validate_als_conf(dict(alpha=alpha, factors=factors, regularization=regularization, n_iterations=n_iterations,
+                               use_gpu=use_gpu))
+        self.alpha, self.factors = float(alpha), int(factors)
+        self.regularization, self.n_iterations = float(regularization), int(n_iterations)
         self.use_gpu = bool(use_gpu)      # the reference's flag; the fit runs on the device whatever it says
         self.name = 'AlternatingLeastSquare'
-        self.users_factors = None     # fp64 [n_users, k] on the device; a view of an even-stride buffer
-        self.items_factors = None     # fp64 [n_items, k]
         logging.info('Built %s: alpha %g, factors %d, regularization %g, n_iterations %d', self.name, self.alpha,
                      self.factors, self.regularization, self.n_iterations)
 
@@ -299,8 +208,9 @@ class AlternatingLeastSquare(FittedRecommenderAlgorithm):
     def _gram_ws_bytes(self, n_users: int, n_items: int) -> int:
         return max(hip_ops.svd_gram_ws_bytes(n, self.factors) for n in (n_users, n_items))
 
-    def _forget(self):
-        self.users_factors = self.items_factors = None
+    def hyper(self) -> dict:
+        return dict(alpha=np.float64(self.alpha), factors=np.int64(self.factors),
+                    regularization=np.float64(self.regularization), n_iterations=np.int64(self.n_iterations))
 
     @classmethod
     def init_factors(cls, n_users: int, n_items: int, k: int):
@@ -321,7 +231,7 @@ class AlternatingLeastSquare(FittedRecommenderAlgorithm):
         i_order = torch.from_numpy(np.argsort(-np.bincount(indices, minlength=n_items),
                                               kind='stable').astype(np.int32)).to(dev)
         u0, v0 = self.init_factors(n_users, n_items, k)
-        U, V = _padded(u0, dev), _padded(v0, dev)
+        U, V = self._padded(u0), self._padded(v0)
         ws = torch.empty(max(self._gram_ws_bytes(n_users, n_items) // 8, 2), dtype=torch.float64, device=dev)
         G = torch.empty((k, k), dtype=torch.float64, device=dev)      # launches are stream-ordered: one G serves both sides
         status = hip_ops.new_status(dev)
@@ -337,36 +247,6 @@ class AlternatingLeastSquare(FittedRecommenderAlgorithm):
                              f'the train matrix or the factors are not what the law assumes')
         self.users_factors, self.items_factors = U, V
         self.n_users, self.n_items = n_users, n_items
-
-    # ------------------------------------------------------------------ scoring
-    def score_rows(self, u_idxs: torch.Tensor, excl=None, out=None) -> torch.Tensor:
-        if self.items_factors is None:
-            raise RuntimeError(f'{self.name}: run fit() or load_model_from_path() first')
-        u = u_idxs.to(self.device, torch.int64).contiguous()
-        return hip_ops.svd_score_rows(u, self.users_factors, self.items_factors, excl=excl, out=out,
-                                      status=self._status_word())
-
-    # ------------------------------------------------------------------ persistence
-    def save_model_to_path(self, path: str):
-        """The reference's two keys (mf_algs.py:127-130) plus alg and the hyper-parameters, which its loader ignores."""
-        np.savez(os.path.join(path, 'model.npz'), users_factors=self.users_factors.cpu().numpy(),
-                 items_factors=self.items_factors.cpu().numpy(), alg=np.array('als'), alpha=np.float64(self.alpha),
-                 factors=np.int64(self.factors), regularization=np.float64(self.regularization),
-                 n_iterations=np.int64(self.n_iterations))
-        logging.info('Model Saved')
-
-    def load_model_from_path(self, path: str):
-        """Reads a file written here or by the reference (no `alg` key; `implicit` returns float32 factors -- any float
-        dtype is taken and held as float64)."""
-        with np.load(os.path.join(path, 'model.npz')) as f:       # never with allow_pickle
-            uf, vf, k = _read_factors(f, 'als', self.name, hip_ops.ALS_MAX_FACTORS)
-            if 'factors' in f and int(f['factors']) != k:
-                raise ValueError(f"factors = {int(f['factors'])} of model.npz, but the factors have {k} columns")
-        self._forget()
-        self.factors = k
-        self.n_users, self.n_items = uf.shape[0], vf.shape[0]
-        self.users_factors, self.items_factors = _padded(uf, self.device), _padded(vf, self.device)
-        logging.info('Model Loaded')
 
     @staticmethod
     def build_from_conf(conf: dict, dataset):

@@ -106,6 +106,7 @@ def _tower(layers: List[int]) -> nn.Sequential:
 
 class DeepMatrixFactorization(_HipTables):
     DENSE_KEYS = ('user_vectors.weight', 'item_vectors.weight')   # of a reference-written model.pth
+    validate_conf = staticmethod(validate_dmf_conf)   # its own keys; the SGD defaults apply as for any trained model
 
     def __init__(self, matrix, u_mid_layers: Union[List[int], int], i_mid_layers: Union[List[int], int],
                  final_dimension: int):

@@ -62,33 +62,10 @@ def validate_ecf_conf(conf: dict):
 def parse_conf(conf: dict, alg, dataset) -> dict:
     """alg / dataset are members of AlgorithmsEnum / DatasetsEnum (only .name and alg.value are used)."""
     from hassaku_amd.algorithms.base_classes import SGDBasedRecommenderAlgorithm
-    from hassaku_amd.algorithms.ecf_alg import ECF
-    from hassaku_amd.algorithms.graph_algs import P3alpha, validate_p3alpha_conf
-    from hassaku_amd.algorithms.knn_algs import KNNAlgorithm, validate_knn_conf
-    from hassaku_amd.algorithms.linear_algs import EASE, SLIM, validate_ease_conf, validate_slim_conf
-    from hassaku_amd.algorithms.mf_algs import (AlternatingLeastSquare, SVDAlgorithm, validate_als_conf,
-                                                validate_svd_conf)
-    from hassaku_amd.algorithms.neural_algs import DeepMatrixFactorization
     from hassaku_amd.train.rec_losses import RecommenderSystemLossesEnum
 
     assert 'data_path' in conf, 'Data path is missing from the configuration file'
-    if issubclass(alg.value, KNNAlgorithm):
-        # the neighbourhood models get no SGD defaults (conf/conf_parser.py:121); their own keys are checked here
-        validate_knn_conf(conf)
-    elif issubclass(alg.value, EASE):
-        validate_ease_conf(conf)
-    elif issubclass(alg.value, SLIM):
-        validate_slim_conf(conf)
-    elif issubclass(alg.value, P3alpha):
-        validate_p3alpha_conf(conf)
-    elif issubclass(alg.value, SVDAlgorithm):
-        validate_svd_conf(conf)
-    elif issubclass(alg.value, AlternatingLeastSquare):
-        validate_als_conf(conf)
-    elif issubclass(alg.value, DeepMatrixFactorization):
-        validate_dmf_conf(conf)   # its own keys; the SGD defaults below apply as for any trained model
-    elif issubclass(alg.value, ECF):
-        validate_ecf_conf(conf)   # likewise
+    alg.value.validate_conf(conf)     # the model's own keys (the fitted models get no SGD defaults below)
     conf['alg'] = alg.name
     conf['time_run'] = generate_id()
     conf['dataset'] = dataset.name

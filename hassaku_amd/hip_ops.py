@@ -37,6 +37,14 @@ def _chk(t: Optional[torch.Tensor], dtype, name: str, shape: Optional[Tuple[int,
         raise ValueError(f'{name} has shape {tuple(t.shape)}, expected {tuple(shape)}')
 
 
+def _chk_gram(t: torch.Tensor, name: str) -> Tuple[int, int]:
+    """(n, ld) of a contiguous fp64 matrix [n, ld >= n] on the device: a square matrix in its first n columns."""
+    _chk(t, torch.float64, name)
+    if t.dim() != 2 or t.shape[1] < t.shape[0]:
+        raise ValueError(f'{name} has shape {tuple(t.shape)}, expected [n, ld >= n]')
+    return t.shape[0], t.shape[1]
+
+
 def new_status(device) -> torch.Tensor:
     return torch.zeros(1, dtype=torch.int32, device=device)
 
@@ -1095,9 +1103,8 @@ def ease_gram_f64(C: torch.Tensor, rows: int, r0: int, lam: int, G: torch.Tensor
     _lib.require_gpu()
     lib = _lib.load()
     _chk(C, torch.int32, 'C')
-    _chk(G, torch.float64, 'G')
-    n = G.shape[0]
-    if G.dim() != 2 or G.shape[1] < n or C.dim() != 2 or C.shape[0] < rows or C.shape[1] < n or r0 + rows > n:
+    n, _ = _chk_gram(G, 'G')
+    if C.dim() != 2 or C.shape[0] < rows or C.shape[1] < n or r0 + rows > n:
         raise ValueError(f'G {tuple(G.shape)} / C {tuple(C.shape)} do not hold rows [{r0}, {r0 + rows}) of an n x n Gram')
     _lib.check(lib.hsk_ease_gram_f64(_p(C), rows, n, C.shape[1], r0, int(lam), _p(G), G.shape[1], _stream()),
                'hsk_ease_gram_f64')
@@ -1113,10 +1120,7 @@ def ease_inverse_f64(A: torch.Tensor, status: Optional[torch.Tensor] = None) -> 
     read of the status word) if a pivot was not positive and finite."""
     _lib.require_gpu()
     lib = _lib.load()
-    _chk(A, torch.float64, 'A')
-    if A.dim() != 2 or A.shape[1] < A.shape[0]:
-        raise ValueError(f'A has shape {tuple(A.shape)}, expected [n, ld >= n]')
-    n, ld = A.shape
+    n, ld = _chk_gram(A, 'A')
     own = status is None
     if own:
         status = torch.zeros(1, dtype=torch.int32, device=A.device)
@@ -1132,9 +1136,7 @@ def ease_weights(P: torch.Tensor) -> torch.Tensor:
     """In place B = P / (-diag P) with a zero diagonal."""
     _lib.require_gpu()
     lib = _lib.load()
-    _chk(P, torch.float64, 'P')
-    if P.dim() != 2 or P.shape[1] < P.shape[0]:
-        raise ValueError(f'P has shape {tuple(P.shape)}, expected [n, ld >= n]')
+    _chk_gram(P, 'P')
     nd = torch.empty(P.shape[0], dtype=torch.float64, device=P.device)
     _lib.check(lib.hsk_ease_weights(_p(P), P.shape[0], P.shape[1], _p(nd), _stream()), 'hsk_ease_weights')
     return P
@@ -1150,10 +1152,7 @@ def _gather_score_rows(users, x_csr, W, name, scale, window, excl, out, status):
     xp, xi, n_users = x_csr
     _chk(xp, torch.int64, 'x_indptr', (n_users + 1,))
     _chk(xi, torch.int32, 'x_indices')
-    _chk(W, torch.float64, name)
-    if W.dim() != 2 or W.shape[1] < W.shape[0]:
-        raise ValueError(f'{name} has shape {tuple(W.shape)}, expected [n_items, ld >= n_items]')
-    n_items = W.shape[0]
+    n_items, _ = _chk_gram(W, name)
     if scale is not None:
         inv_deg_u, alpha = scale
         if inv_deg_u.numel() < n_users:
@@ -1422,10 +1421,7 @@ def slim_cd(G: torch.Tensor, l1: float, l2: float, tol: float, max_iter: int, j0
     HSK_STATUS_NOT_FINITE (16); without a caller's word a set bit raises ArithmeticError here."""
     _lib.require_gpu()
     lib = _lib.load()
-    _chk(G, torch.float64, 'G')
-    if G.dim() != 2 or G.shape[1] < G.shape[0]:
-        raise ValueError(f'G has shape {tuple(G.shape)}, expected [n, ld >= n]')
-    n, ld = G.shape
+    n, ld = _chk_gram(G, 'G')
     j1 = n if j1 is None else j1
     if out is None:
         out = torch.zeros((n, n), dtype=torch.float64, device=G.device)

@@ -20,7 +20,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hassaku_amd import hip_ops  # noqa: E402
-from hassaku_amd.algorithms.base_classes import csr_transpose  # noqa: E402
+from hassaku_amd.algorithms.base_classes import csr_arrays  # noqa: E402
 from hassaku_amd.algorithms.linear_algs import EASE  # noqa: E402
 from hassaku_amd.data.csr import UserItemCsr  # noqa: E402
 from hassaku_amd.data.synthetic import generate_named  # noqa: E402
@@ -32,28 +32,18 @@ def _now():
 
 
 def time_fit(model, train):
-    """(phase -> seconds, G on the device before the inverse) with the steps of EASE.fit timed separately."""
-    dev = model.device
-    n_users, n = train.n_rows, train.n_cols
-    x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
+    """(phase -> seconds, G on the host before the inverse): the phase methods EASE.fit calls, timed one by one."""
     t0 = _now()
-    t_ptr, t_idx, _ = csr_transpose(x_ptr, x_idx, None, n_users, n)
-    M = hip_ops.knn_pack_i8(t_ptr, t_idx, n, n_users)
+    _, _, M = model._pack(*csr_arrays(train))
     t1 = _now()
-    block = model._gram_block(n)
-    C = torch.empty((block, n), dtype=torch.int32, device=dev)
-    G = torch.empty((n, n), dtype=torch.float64, device=dev)
-    for r0 in range(0, n, block):
-        r1 = min(r0 + block, n)
-        hip_ops.knn_gram_i8(M, n, r0, r1, out=C)
-        hip_ops.ease_gram_f64(C, r1 - r0, r0, model.lam_int, G)
+    G = model._gram_f64(M, train.n_cols, model.lam_int)
     t2 = _now()
-    del M, C
+    del M
     G_host = G.cpu().numpy()
     t3 = _now()
-    hip_ops.ease_inverse_f64(G)
+    model._inverse(G)
     t4 = _now()
-    hip_ops.ease_weights(G)
+    model._weights(G)
     t5 = _now()
     return {'pack_s': t1 - t0, 'gram_s': t2 - t1, 'inverse_s': t4 - t3, 'weights_s': t5 - t4}, G_host
 

@@ -14,12 +14,11 @@ import os
 import sys
 import time
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hassaku_amd import hip_ops  # noqa: E402
-from hassaku_amd.algorithms.base_classes import csr_transpose  # noqa: E402
+from hassaku_amd.algorithms.base_classes import csr_arrays  # noqa: E402
 from hassaku_amd.algorithms.knn_algs import ItemKNN, UserKNN  # noqa: E402
 from hassaku_amd.data.csr import UserItemCsr  # noqa: E402
 from hassaku_amd.data.synthetic import generate_named  # noqa: E402
@@ -34,29 +33,21 @@ def _now():
 
 
 def time_fit(model, train):
-    """(phase -> seconds, gram int8 ops) of one fit, phases timed separately (same steps as KNNAlgorithm.fit)."""
-    dev = model.device
-    x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
+    """(phase -> seconds, gram int8 ops) of one fit: the phase methods KNNAlgorithm.fit calls, timed one by one."""
     t0 = _now()
-    if model.ITEM_BASED:
-        e_ptr, e_idx, _ = csr_transpose(x_ptr, x_idx, None, train.n_rows, train.n_cols)
-        n_ent, n_feat = train.n_cols, train.n_rows
-    else:
-        e_ptr, e_idx, n_ent, n_feat = x_ptr, x_idx, train.n_rows, train.n_cols
-    deg = torch.diff(e_ptr)
-    sq = torch.sqrt(deg.double())
-    M = hip_ops.knn_pack_i8(e_ptr, e_idx, n_ent, n_feat)
+    M, n_ent, degrees = model._pack(*csr_arrays(train))
     t1 = _now()
-    block = max(128, (model.GRAM_BLOCK_BYTES // (4 * n_ent)) // 128 * 128)
-    C = torch.empty((min(block, n_ent), n_ent), dtype=torch.int32, device=dev)
     gram = select = 0.
     ops = 0
-    for r0 in range(0, n_ent, block):
-        r1 = min(r0 + block, n_ent)
+    blocks = model._count_blocks(M, n_ent)
+    while True:
         a = _now()
-        hip_ops.knn_gram_i8(M, n_ent, r0, r1, out=C)
+        block = next(blocks, None)        # one launch of the Gram kernel
         b = _now()
-        hip_ops.knn_select(C, r1 - r0, r0, deg, sq, None, None, 'cosine', None, None, model.shrinkage, model.k)
+        if block is None:
+            break
+        r0, r1, C = block
+        model._select(C, r0, r1, degrees)
         c = _now()
         gram += b - a
         select += c - b

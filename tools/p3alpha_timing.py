@@ -40,7 +40,7 @@ def worker(opts):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from hassaku_amd import hip_ops
     from hassaku_amd.algorithms.graph_algs import P3alpha
-    from hassaku_amd.algorithms.base_classes import csr_transpose
+    from hassaku_amd.algorithms.base_classes import csr_arrays
     from hassaku_amd.data.csr import UserItemCsr
     from hassaku_amd.data.synthetic import generate_named
 
@@ -83,18 +83,13 @@ def worker(opts):
     del buf
     torch.cuda.empty_cache()
 
-    # the steps of fit, one by one
-    x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
+    # the phase methods P3alpha.fit calls, one by one
     t0 = now()
-    t_ptr, t_idx, _ = csr_transpose(x_ptr, x_idx, None, n_users, n)
-    M = hip_ops.knn_pack_i8(t_ptr, t_idx, n, n_users)
+    (x_ptr, _), t_ptr, M = model._pack(*csr_arrays(train))
     t1 = now()
-    w_u = hip_ops.p3_inv_degrees(x_ptr, M.shape[1])
-    w_i = hip_ops.p3_inv_degrees(t_ptr)
+    w_u, w_i = model._degrees(x_ptr, t_ptr, M.shape[1])
     t2 = now()
-    W = torch.empty((n, n), dtype=torch.float64, device=dev)
-    for r0 in range(0, n, model.GRAM_BLOCK_ROWS):
-        hip_ops.p3_gram_f64(M, n, w_u, r0, min(r0 + model.GRAM_BLOCK_ROWS, n), W, row_scale=w_i)
+    W = model._weighted_gram(M, n, w_u, w_i)
     t3 = now()
     k_pad = int(M.shape[1])
     gram_flop = 2 * n * n * k_pad

@@ -18,7 +18,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hassaku_amd import hip_ops  # noqa: E402
-from hassaku_amd.algorithms.base_classes import csr_transpose  # noqa: E402
+from hassaku_amd.algorithms.base_classes import csr_arrays  # noqa: E402
 from hassaku_amd.algorithms.linear_algs import SLIM  # noqa: E402
 from hassaku_amd.data.csr import UserItemCsr  # noqa: E402
 from hassaku_amd.data.synthetic import generate_named  # noqa: E402
@@ -27,22 +27,6 @@ from hassaku_amd.data.synthetic import generate_named  # noqa: E402
 def _now():
     torch.cuda.synchronize()
     return time.perf_counter()
-
-
-def gram(model, train):
-    dev = model.device
-    n_users, n = train.n_rows, train.n_cols
-    x_ptr, x_idx = (torch.from_numpy(a).to(dev) for a in (train.indptr, train.indices))
-    t_ptr, t_idx, _ = csr_transpose(x_ptr, x_idx, None, n_users, n)
-    M = hip_ops.knn_pack_i8(t_ptr, t_idx, n, n_users)
-    block = model._gram_block(n)
-    C = torch.empty((block, n), dtype=torch.int32, device=dev)
-    G = torch.empty((n, n), dtype=torch.float64, device=dev)
-    for r0 in range(0, n, block):
-        r1 = min(r0 + block, n)
-        hip_ops.knn_gram_i8(M, n, r0, r1, out=C)
-        hip_ops.ease_gram_f64(C, r1 - r0, r0, 0, G)
-    return G
 
 
 def candidate_counts(G, l1, rows=1024):
@@ -81,10 +65,10 @@ def main():
                'weights_kept': int((W > 0).sum()), 'weights_per_column_mean': float((W > 0).sum(0).double().mean())}
         model.W = W = None
         torch.cuda.empty_cache()
-        G = gram(model, train)
+        G, _ = model._gram(*csr_arrays(train), 0)      # the phase methods SLIM.fit calls
         l1, l2 = model.penalties(d.n_users)
         t0 = _now()
-        hip_ops.slim_cd(G, l1, l2, model.tol, opts.max_iter)
+        model._solve(G, d.n_users)
         out['solver_s'] = _now() - t0
         counts = candidate_counts(G, l1)
         out.update(l1=l1, l2=l2, candidates_mean=float(counts.double().mean()), candidates_max=int(counts.max()),
