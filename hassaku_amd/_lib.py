@@ -44,7 +44,7 @@ class HskBprmfState(ctypes.Structure):
         # library scratch (zero-initialised by ctypes, never written from Python)
         ('frozen_hyper', c_double * 5), ('frozen_opt', c_int32), ('frozen_valid', c_int32),
         ('timing_now', c_int32), ('item_pair', c_int32),
-        ('fwd_overlap', c_int32), ('reserved0', c_int32),
+        ('fwd_overlap', c_int32), ('item_lists', c_int32),
     ]
 
 

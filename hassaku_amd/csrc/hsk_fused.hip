@@ -31,7 +31,10 @@
 #ifndef HSK_FWD_OVERLAP_DEFAULT
 #define HSK_FWD_OVERLAP_DEFAULT 1   // the overlapped gather loop of k_fwd_part unless st->fwd_overlap / HSK_FWD_OVERLAP say otherwise
 #endif
-#define HSK_ADAM_TAB_LEN 65536   // per-step (step_size, bc2_sqrt) table for the lazy replay
+#ifndef HSK_ITEM_LISTS_DEFAULT
+#define HSK_ITEM_LISTS_DEFAULT 1   // k_item_lists in front of the pair form's launch unless st->item_lists / HSK_ITEM_LISTS say otherwise
+#endif
+#define HSK_ADAM_TAB_LEN 65536  // per-step (step_size, bc2_sqrt) table for the lazy replay
 #define HSK_FLUSH_NEVER (1 << 30) // cadence of a table whose periodic sweep never pays (an explicit flush still sweeps)
 
 // =============================================================================================
@@ -119,6 +122,10 @@ struct hsk_ws {
   // third set (single-GPU step only): the in-launch preparation pipeline works on the batches of THREE steps at a time
   int *u32_c, *it32_c, *perm_c, *hist_c, *btot_c, *bstart_c, *offsets_c, *owner_c, *cnt_c, *stamp_c;
   int2* perm1_c;
+  // the step's item lists written out in list order (k_item_lists, hsk_item_sliced.h): entry weights and batch positions
+  // by sorted position.  One pair, not one per set: produced and consumed inside one step
+  float* wl;
+  int* ul;
   int64_t total;
 };
 
@@ -238,6 +245,8 @@ static hsk_ws hsk_carve(void* base, int64_t n_users, int64_t n_items, int64_t di
   w.owner_c = (int*)take(c3 * n_users * 4);
   w.cnt_c = (int*)take(c3 * n_users * 4);
   w.stamp_c = (int*)take(c3 * n_users * 4);
+  w.wl = (float*)take(c3 * ent * 4);   // (the sharded step's item pass never takes the pair form)
+  w.ul = (int*)take(c3 * ent * 4);
   w.total = off;
   return w;
 }
@@ -715,8 +724,8 @@ static int hsk_periodic_flush(hsk_bprmf_state* st, const hsk_ws& w, hipStream_t 
 // the form hsk_launch_item_pass chose (whole_rows / part / pair); nblk: the item workgroups
 template <int V, int NCH, bool FULL>
 static void hsk_launch_item_user(const hsk_item_args& ia, const hsk_user_lazy_args& ua, const hsk_ahead_args& ahead,
-                                 const hsk_ride_item* ri, unsigned nblk, bool whole_rows, bool part, bool pair, bool gen,
-                                 bool lazy, hipStream_t stream) {
+                                 const hsk_ride_item* ri, unsigned nblk, bool whole_rows, bool part, bool pair, bool lists,
+                                 bool gen, bool lazy, hipStream_t stream) {
   constexpr int VSC = (V == 4) ? 4 : 2;
   const int dense = ua.n_users > 0;
   const int nub = (int)hsk_align_up(hsk_ceil_div(dense ? ua.n_users : ua.B, 4) + 1, 8);
@@ -729,15 +738,16 @@ static void hsk_launch_item_user(const hsk_item_args& ia, const hsk_user_lazy_ar
   const int nab_big = ahead.coo_user ? (int)hsk_align_up(hsk_ceil_div(ahead.n, 4), 8) : 0;   // large-batch kernel
 
   if (pair) {
-    if constexpr (V == 4) {
-      if (part) {
-        if constexpr (FULL)
-          k_item_user_pair<NCH, FULL, true><<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, stream>>>(
+    if constexpr (V == 4)
+      hsk_dispatch_flags([&](auto part_, auto lists_) {
+        constexpr bool PART = decltype(part_)::value, LISTS = decltype(lists_)::value;
+        if constexpr (!PART)
+          k_item_user_pair<NCH, FULL, false, LISTS><<<nblk + (unsigned)nub, 256, 0, stream>>>(ia, ua, nub, dense);
+        else if constexpr (FULL)
+          k_item_user_pair<NCH, FULL, true, LISTS><<<nblk + (unsigned)nub + (unsigned)(ri ? ri->n_total : 0), 256, 0, stream>>>(
               ia, ua, nub, dense, ri ? *ri : hsk_ride_item{});
-      } else {
-        k_item_user_pair<NCH, FULL><<<nblk + (unsigned)nub, 256, 0, stream>>>(ia, ua, nub, dense);
-      }
-    }
+        return HSK_OK;
+      }, part, lists);
     return;
   }
   hsk_dispatch_flags([&](auto gen_, auto lz_) {
@@ -811,19 +821,31 @@ static void hsk_launch_item_pass(const hsk_bprmf_state* st, const hsk_ws& w, con
                                                               : hot > HSK_ITEM_PAIR_HOT_BYTES && n_entries >= 8 * (int64_t)I;
   }
   if (pair) n_sl = (int)hsk_ceil_div(D, 128);
+  // the pair form's weights and user rows in list order, written once by k_item_lists in front of the merged launch
+  // (hsk_item_sliced.h) instead of gathered through perm by every (item, slice) wave: on wherever the pair form is
+  // taken; st->item_lists (1 / -1) and HSK_ITEM_LISTS (1 / 0) force it on / off, the state's field first.  Same bits.
+  static const int lists_env = hsk_env_int("HSK_ITEM_LISTS", -1);
+  const bool lists = pair && (st->item_lists ? st->item_lists > 0 : lists_env >= 0 ? lists_env != 0 : HSK_ITEM_LISTS_DEFAULT != 0);
   const int n_slices_pad = whole_rows ? 0 : (n_sl < 8 && 8 % n_sl == 0) ? n_sl : (int)hsk_align_up(n_sl, 8);
   // lazy item AdamW: only the items with entries (the sort's `touched` list; at most one per entry)
   const int64_t n_list = lazy ? std::min<int64_t>(I, n_entries) : I;
   const unsigned groups = (unsigned)hsk_align_up(hsk_ceil_div(n_list, 4 * ipw), 8);
+  if (lists) {
+    // (an ordinary launch under capture: ua->desc is the replayed graph's step descriptor)
+    const int n_ent = (int)n_entries;
+    hsk_launch_ev(k_item_lists, dim3((unsigned)hsk_ceil_div(n_ent, 256)), dim3(256), 0, stream, ua->desc != nullptr, nullptr,
+                  nullptr, w.perm, w.g_s, w.offsets, I, n_ent, K, hsk_make_div_magic(K), n_part, w.wl, w.ul);
+  }
   const hsk_item_args ia = {Urows, st->item_emb, st->item_bias, st->m_item_emb, st->v_item_emb, st->m_item_bias,
-                            st->v_item_bias, urow_index, w.g_s, w.perm, w.offsets, I, K, D, n_slices_pad, ipw, c,
+                            st->v_item_bias, urow_index, lists ? w.wl : w.g_s, lists ? w.ul : w.perm, w.offsets, I, K, D,
+                            n_slices_pad, ipw, c,
                             gI_out, gIb_out, w.touched, w.n_touched, w.last_step_i, (int)st->step, w.pend,
                             ua ? ua->desc : nullptr, ua ? ua->rel : 0, w.adam_tab, HSK_ADAM_TAB_LEN, n_part};
   const unsigned nblk = groups * (whole_rows ? 1 : n_slices_pad);
   if (APPLY && ua) {
     if constexpr (APPLY)
-      hsk_launch_item_user<V, NCH, FULL>(ia, *ua, aa ? *aa : hsk_ahead_args{}, ri, nblk, whole_rows, part, pair, gen, lazy,
-                                         stream);
+      hsk_launch_item_user<V, NCH, FULL>(ia, *ua, aa ? *aa : hsk_ahead_args{}, ri, nblk, whole_rows, part, pair, lists, gen,
+                                         lazy, stream);
     return;
   }
   // lazy item AdamW without the user update in the launch (the sharded step): whole rows, as in the merged launch above

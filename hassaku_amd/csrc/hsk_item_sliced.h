@@ -39,7 +39,7 @@ struct hsk_item_args {
   const float* Uw;        // user rows: the table (+ u32), an exchange buffer (+ slot index) or ucur (u32 == NULL)
   float* Iw; float* Ib; float* mI; float* vI; float* mIb; float* vIb;
   const int* u32;         // row of Uw for batch position e / K; NULL: the position itself
-  const float* g_s; const int* perm; const int* offsets;
+  const float* g_s; const int* perm; const int* offsets;   // (pair form with LISTS: k_item_lists' wl and ul as g_s and perm)
   int n_items, K, D, n_slices_pad, items_per_wave;
   hsk_adamw_consts c;
   float* gI_out; float* gIb_out;
@@ -249,9 +249,45 @@ __device__ __forceinline__ void hsk_pair_gather(const float* __restrict__ Uw, in
   }
 }
 
+// ---- the lists' weights and user rows, once per step and in list order ---------------------------------------------
+// Every (item, slice) wave of the pair form reads its chunk's weights as g_s[perm[c]]: a scattered dword per entry, one
+// 128-byte L2 request for 4 bytes, n_part - 1 more for a positive, and D / 128 slices repeat it.  k_item_lists does it
+// once: thread c < the sort's entry count writes wl[c] = the weight hsk_entry_weight<PART> gives entry perm[c] (the same
+// adds in the same order) and ul[c] = its batch position.  The item waves (hsk_item_pair_body<PART, LISTS = true>) then
+// read wl / ul with two coalesced loads per chunk, and g_s, perm, the division and the positive's share loop leave them.
+// e / K as a multiply: mul = ceil(2^(31 + l) / K) with 2^l >= K, shift = l - 1 (hsk_div_magic; exact for 0 <= e < 2^31).
+struct hsk_div_magic {
+  unsigned mul;
+  int shift;
+};
+static inline hsk_div_magic hsk_make_div_magic(int K) {   // K >= 2
+  int l = 1;
+  while ((1ll << l) < K) ++l;
+  return {(unsigned)((((unsigned long long)1 << (31 + l)) + (unsigned)K - 1) / (unsigned)K), l - 1};
+}
+
+// perm / offsets: the sort's (offsets[n_items] = the entries with an item id; perm holds nothing behind them);
+// n_entries = B * K, the size of g_s, wl and ul
+__global__ __launch_bounds__(256) void k_item_lists(const int* __restrict__ perm, const float* __restrict__ g_s,
+                                                    const int* __restrict__ offsets, int n_items, int n_entries, int K,
+                                                    hsk_div_magic kd, int n_part, float* __restrict__ wl,
+                                                    int* __restrict__ ul) {
+  const int c = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (c >= min(n_entries, hsk_uniform_i(offsets[n_items]))) return;
+  const int e = perm[c];
+  if ((unsigned)e >= (unsigned)n_entries) return;   // (never, by the sort; keeps every read below inside g_s)
+  const int bpos = (int)(__umulhi((unsigned)e, kd.mul) >> kd.shift);
+  float g = g_s[e];
+  if (e == bpos * K)   // a positive's entry: columns 1 .. n_part-1 of its row hold the other units' shares
+    for (int q = 1; q < n_part; ++q) g += g_s[e + q];
+  wl[c] = g;
+  ul[c] = bpos;
+}
+
 // AdamW item pass (APPLY, no GEN, every item) on V = 4 rows; arguments and workgroup numbering of hsk_item_sliced_body
-// with n_slices_pad counted in 128-float slices.
-template <bool PART>
+// with n_slices_pad counted in 128-float slices.  LISTS: a.g_s and a.perm are k_item_lists' wl and ul, indexed by
+// sorted position.
+template <bool PART, bool LISTS = false>
 __device__ __forceinline__ void hsk_item_pair_body(const hsk_item_args& a, int bid) {
   const float* __restrict__ Uw = a.Uw;
   float* __restrict__ Iw = a.Iw;
@@ -313,10 +349,15 @@ __device__ __forceinline__ void hsk_item_pair_body(const hsk_item_args& a, int b
       int myu = 0;
       float myg = 0.f;
       if (lane < nr) {
-        const int e = perm[c0 + lane];
-        const int bpos = e / K;
-        myg = PART ? hsk_entry_weight<true>(a, e, bpos) : g_s[e];
-        myu = bpos;   // the user rows are laid out by batch position (ucur), fewer than 2^30 floats of them
+        if constexpr (LISTS) {   // k_item_lists left both in list order
+          myg = g_s[c0 + lane];
+          myu = perm[c0 + lane];
+        } else {
+          const int e = perm[c0 + lane];
+          const int bpos = e / K;
+          myg = PART ? hsk_entry_weight<true>(a, e, bpos) : g_s[e];
+          myu = bpos;   // the user rows are laid out by batch position (ucur), fewer than 2^30 floats of them
+        }
       }
       gb_lane += myg;
       int j = 0;
@@ -501,8 +542,8 @@ void k_item_user(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks, int
 
 // k_item_user<4, NCH, FULL, 4, false, false, PART> with the pair form of the item pass (hsk_item_pair_body): AdamW on
 // every item, rows of D % 4 == 0.  A kernel of its own and not a flag of k_item_user, whose instantiations keep the
-// code they had.
-template <int NCH, bool FULL, bool PART = false>
+// code they had.  LISTS: the lists' weights and user rows come in list order from k_item_lists (hsk_item_pair_body).
+template <int NCH, bool FULL, bool PART = false, bool LISTS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_item_user_pair(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks, int dense_users, hsk_ride_item ri = hsk_ride_item{}) {
   constexpr int POL_OWNER = hsk_stream_policy(HSK_STREAM_OWNER);
@@ -526,7 +567,7 @@ void k_item_user_pair(hsk_item_args ia, hsk_user_lazy_args ua, int n_user_blocks
       hsk_user_update_lazy_body<4, NCH, FULL, false, PART, POL_OWNER>(ua, bid);
     return;
   }
-  hsk_item_pair_body<PART>(ia, bid - n_user_blocks);
+  hsk_item_pair_body<PART, LISTS>(ia, bid - n_user_blocks);
 }
 
 // small batches: whole-row item workgroups, interleaved with the ahead workgroups

@@ -574,7 +574,10 @@ class BprMfFusedState:
         # form of the large-batch item pass: 0 by the library's rule, 1 / -1 the pair form forced on / off (same bits)
         st.item_pair = 0
         # gather loop of the large-batch forward: 0 the library's choice, 1 / -1 the overlapped loop on / off (same bits)
-        st.fwd_overlap, st.reserved0 = 0, 0
+        st.fwd_overlap = 0
+        # the pair form's list weights / user rows: 0 the library's choice, 1 / -1 written in list order by a launch of
+        # their own (k_item_lists) / gathered by every item wave (same bits)
+        st.item_lists = 0
         # steps between the periodic sweeps of the lazily updated tables; 0: from the table / batch sizes
         # (hsk_bprmf_flush_cadence; a speed matter only -- every cadence gives the same bits)
         st.flush_every, st.ws_sharded = int(flush_every), 0

@@ -311,7 +311,13 @@ typedef struct hsk_bprmf_state {
      other buffer's loads stay in flight while one is weighed) wherever it exists; -1: the loop with a test per row.
      Bit-identical results */
   int32_t fwd_overlap;
-  int32_t reserved0;   /* zero; keeps the state free of padding holes */
+  /* CALLER-OWNED option in the place of the reserved word (the layout and the size are what they were): where the pair
+     form of the item pass finds its lists' weights and user rows.  0 (default): the library's choice, or the
+     environment's HSK_ITEM_LISTS = 0 / 1; 1: a small launch in front of the item / user launch (k_item_lists) writes
+     them once per step in list order, and the item waves read them with two coalesced loads per chunk; -1: every item
+     wave gathers them itself through the sort's permutation.  No effect where the pair form is not taken.
+     Bit-identical results */
+  int32_t item_lists;
 } hsk_bprmf_state;
 
 int64_t hsk_bprmf_workspace_bytes(int64_t n_users, int64_t n_items, int64_t dim,
