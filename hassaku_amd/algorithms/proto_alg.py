@@ -53,9 +53,8 @@ class _HipTables(SGDBasedRecommenderAlgorithm):
         return self._status
 
     def check_indices(self):
-        if self._status is not None:
-            hip_ops.raise_on_status(self._status, self.name)
-            self._status.zero_()
+        """Raise IndexError if a kernel saw an out-of-range index since the last check; the word is clear afterwards."""
+        hip_ops.check_and_clear_status(self._status, self.name)
 
     def lookup(self, table: nn.Embedding, idx: torch.Tensor) -> torch.Tensor:
         return hip_ops.embedding(table.weight, idx, self.status_word())

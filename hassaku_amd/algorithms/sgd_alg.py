@@ -93,9 +93,9 @@ class SGDBaseline(SGDBasedRecommenderAlgorithm):
         return self._status
 
     def check_indices(self):
-        if self._status is not None:
-            hip_ops.raise_on_status(self._status, self.name)
-            self._status.zero_()
+        """Raise IndexError if a kernel saw an out-of-range index since the last check (one host sync); the word is
+        clear afterwards either way."""
+        hip_ops.check_and_clear_status(self._status, self.name)
 
     def get_user_representations(self, u_idxs: torch.Tensor) -> UserRepr:
         return UserRepr(u_idxs)
@@ -154,10 +154,9 @@ class SGDMatrixFactorization(SGDBasedRecommenderAlgorithm):
         return self._status
 
     def check_indices(self):
-        """Raise IndexError if a kernel saw an out-of-range index since the last check (one host sync)."""
-        if self._status is not None:
-            hip_ops.raise_on_status(self._status, self.name)
-            self._status.zero_()
+        """Raise IndexError if a kernel saw an out-of-range index since the last check (one host sync); the word is
+        clear afterwards either way."""
+        hip_ops.check_and_clear_status(self._status, self.name)
 
     # -- plugin surface ------------------------------------------------------------------------
     def get_user_representations(self, u_idxs: torch.Tensor) -> UserRepr:

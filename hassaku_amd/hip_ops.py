@@ -58,6 +58,17 @@ def raise_on_status(status: torch.Tensor, what: str = ''):
         raise RuntimeError(f'{what}: negative sampler gave up (a user interacted with ~every item)')
 
 
+def check_and_clear_status(status: Optional[torch.Tensor], what: str = ''):
+    """raise_on_status for a word that outlives the check (a model's): what it has seen "since the last check".  A set
+    word is cleared BEFORE the raise -- left set, it would fail every later check of a model that has seen one bad
+    index.  One host sync when the word is clear; a read that fails itself leaves the word alone."""
+    if status is None or int(status.item()) == 0:
+        return
+    seen = status.clone()
+    status.zero_()
+    raise_on_status(seen, what)
+
+
 # ------------------------------------------------------------------------------------------------
 # un-fused operators
 # ------------------------------------------------------------------------------------------------

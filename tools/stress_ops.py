@@ -27,10 +27,15 @@ def close(a, b, tol, what):
 
 
 def case_scores(rng, g):
-    D = int(rng.choice([1, 2, 6, 16, 30, 33, 64, 100, 128, 200, 256, 402, 512, 1024]))
+    D = int(rng.choice([1, 2, 6, 16, 30, 33, 64, 100, 128, 200, 256, 402, 511, 512, 1022, 1024, 2048]))
     U, I = int(rng.randint(1, 400)), int(rng.randint(8, 600))   # (two or three items: every gradient is a near-total
     # cancellation and 'relative to the largest element' stops meaning anything)
-    B, K = int(rng.randint(1, 300)), int(rng.randint(2, 60))
+    # K: mostly short rows, and both sides of a wave's 128 columns and of a workgroup's 512 -- those with B < 40, so that
+    # an item's gradient stays a sum of at most ~2500 entries, as with the short rows: past that the cancellation between
+    # the entries of a small catalogue outgrows 2e-5 of the largest element by rounding alone (2.1e-5 ... 3.5e-5
+    # at 3400 ... 15 900 entries per item: MEASUREMENTS section 5.3), and the float64 reference below gathers [B, K, D]
+    K = int(rng.choice([int(rng.randint(2, 60))] * 6 + [127, 128, 129, 511, 512, 513]))
+    B = int(rng.randint(1, 300 if K < 60 else 40))
     ue = torch.randn(U, D, device='cuda', generator=g) * 0.3
     ie = torch.randn(I, D, device='cuda', generator=g) * 0.3
     ib = torch.randn(I, device='cuda', generator=g) * 0.1 if rng.rand() < 0.7 else None
